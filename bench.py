@@ -17,6 +17,11 @@ under an external launcher (WORLD_SIZE set) each process is one rank.  The whole
 against a deadline (CHR_BENCH_DEADLINE_S, default 240 s from the launch): context entries that
 would start after it are recorded as {"skipped": "deadline"}, never the metric.
 
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if given and prints the line.
+--full adds what the headline figure does not need: the CPU baseline, the result checks of the metric's
+output and, at N>1, the profiled call behind `roofline` / `phase_transfer_ms` and the `compare` context lines
+(--no-cpu-baseline and --no-compare leave those two out of a --full run).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -51,13 +56,20 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
-    p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (profiling runs)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the metric: the CPU baseline, the result checks of the metric's output and, at N>1, "
+                        "the profiled call behind the roofline and the same-run context lines.  Without it a run "
+                        "sets up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; "
+                        "a fixed seeded sample of 8 Mi elements of a larger output; rank 0 at N>1)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--sweep", action="store_true", help="N=1: bucket sizes 1 KiB..1 GiB, m=1/3/7 (table to stderr)")
     p.add_argument("--count", type=int, default=None, help="N>1: elements per rank (default 2^28)")
     p.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
     p.add_argument("--no-compare", action="store_true",
-                   help="N>1: skip the same-run context lines (RCCL allreduce, MPICH ring on libchiara)")
+                   help="N>1 --full: skip the same-run context lines (RCCL allreduce, MPICH ring on libchiara)")
     p.add_argument("--phases", action="store_true",
                    help="N>1: add CHiArA's stand-alone phases (phase 1, phase 2, the k-nomial scatter) to the "
                         "context lines")
@@ -250,7 +262,9 @@ def line_problems(line, rccl_library=True):
         if r.get("xgmi") is False and not r.get("not_xgmi_because"):
             probs.append("rccl.xgmi false without a reason")
         rc = line.get("result_check")
-        if not isinstance(rc, dict):
+        if rc is None and line.get("full") is False:
+            pass  # a run without --full makes no result check; lines from before the option are full
+        elif not isinstance(rc, dict):
             probs.append("result_check missing")
         elif not (rc.get("ranks_bit_identical") and rc.get("within_tolerance")):
             probs.append(f"result_check failed: {rc}"[:300])
@@ -335,6 +349,24 @@ def pmc_traffic(kernel_key, symbol, root=REPO):
     return pmc_provenance.current_traffic(entry, kernel_key, symbol, root)
 
 
+DUMP_MAX_ELEMS = 8 << 20     # --dump-outputs: at most 32 MiB of float32 per array
+
+
+def dump_outputs(torch, out_dir, name, out):
+    """--dump-outputs: the 1-D device tensor `out` (what the last timed step handed its caller) as
+    out_dir/<name>.npy in float32 -- all of it up to DUMP_MAX_ELEMS elements, else the elements at DUMP_MAX_ELEMS
+    positions drawn once from SEED and the length (sorted), so two runs with the same arguments write the same
+    positions of the same inputs' result."""
+    import numpy as np
+
+    n = out.numel()
+    if n > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(SEED).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), out.float().cpu().numpy())
+
+
 # ---- N = 1: bucket reduction (C2) ----------------------------------------------------------------
 
 def bench_bucket(args, cpu):
@@ -394,6 +426,8 @@ def bench_bucket(args, cpu):
     avg_kern_ms = total_ms / args.steps
     bytes_per_step = 3 * 4 * n
     ms_per_step = total_ms / args.steps
+    if args.dump_outputs:  # the accumulator the last timed call reduced into, before anything else touches it
+        dump_outputs(torch, args.dump_outputs, "acc", accs[(args.steps - 1) % NSETS])
     achieved = bytes_per_step / (avg_kern_ms * 1e-3) / 1e9
     traffic, stale = pmc_traffic("reduce_f32_sum_m1_64MiB", C2_KERNEL_SYMBOL)
     line = {
@@ -413,10 +447,12 @@ def bench_bucket(args, cpu):
         "definitions": LINE_DEFINITIONS_N1,
         "cpu_baseline": cpu,
         "host_wall_s": round(wall, 4),
+        "full": bool(args.full),  # --full: cpu_baseline and result_check beside the metric
     }
     if stale:
         line["roofline"]["traffic_stale"] = stale
-    line["result_check"] = bucket_result_check(torch, ca, accs[0], ins[0], n, stream)
+    if args.full:
+        line["result_check"] = bucket_result_check(torch, ca, accs[0], ins[0], n, stream)
     if cpu:
         line["gpu_vs_cpu"] = round(line["value"] / cpu["value"], 1)
         if "all_cores" in cpu:
@@ -1134,29 +1170,37 @@ def bench_allreduce(args):
     S = count * es
     algbw = S * args.steps / el / 1e9
     busbw = algbw * 2 * (world - 1) / world
-    # roofline of the dominant OUR kernel inside the collective: one more (untimed) call
+    if args.dump_outputs and rank == 0:  # what the last timed call left in rank 0's recv
+        dump_outputs(torch, args.dump_outputs, "recv",
+                     recv[:count * es].view(torch.float32 if es == 4 else torch.bfloat16))
+    # roofline of the dominant OUR kernel inside the collective (--full): one more (untimed) call
     # with HIP events around every fused reduction launch on the comm stream
-    comm.profile(True)
-    ca.check(ca.all_reduce_radix_batch(send, recv, count, dt, ca.SUM, comm, k, b, async_op=True))
-    torch.cuda.synchronize()
-    red_ms, red_bytes, red_n = comm.profile_read()
-    phases = comm.profile_phases()  # transfer ms per plan phase (DEBUG_MODE phase timers' analogue)
-    comm.profile(False)
-    # the metric's output on every rank: bit-identical across ranks and within the stated tolerance of
+    red_ms, red_bytes, red_n, phases = 0.0, 0.0, 0, {}
+    if args.full:
+        comm.profile(True)
+        ca.check(ca.all_reduce_radix_batch(send, recv, count, dt, ca.SUM, comm, k, b, async_op=True))
+        torch.cuda.synchronize()
+        red_ms, red_bytes, red_n = comm.profile_read()
+        phases = comm.profile_phases()  # transfer ms per plan phase (DEBUG_MODE phase timers' analogue)
+        comm.profile(False)
+    # the metric's output on every rank (--full): bit-identical across ranks and within the stated tolerance of
     # the fp64 sum (recv holds the last call's result; every call computes the same bits)
-    try:
-        def fill_rank(r, buf):
-            ca.check(ca.fill(buf, count, dt, 0, SEED, r, stream=stream))
-            torch.cuda.synchronize()
-        check = result_check(torch, dist, recv, count, es, world, fill_rank)
-        # and bit for bit against a known answer: one more call of the same configuration on integer-valued inputs
-        check.update(exact_check(
-            torch, dist, send, recv, count, es, rank,
-            lambda: ca.check(ca.all_reduce_radix_batch(send, recv, count, dt, ca.SUM, comm, k, b)), world))
-        fill_rank(rank, send)  # the metric's inputs back for the comparison lines
-    except Exception as e:  # recorded, never hidden: line_problems() flags a line without a passing check
-        check = {"error": str(e)[:200]}
-    torch.cuda.empty_cache()
+    check = None
+    if args.full:
+        try:
+            def fill_rank(r, buf):
+                ca.check(ca.fill(buf, count, dt, 0, SEED, r, stream=stream))
+                torch.cuda.synchronize()
+            check = result_check(torch, dist, recv, count, es, world, fill_rank)
+            # and bit for bit against a known answer: one more call of the same configuration on integer-valued
+            # inputs
+            check.update(exact_check(
+                torch, dist, send, recv, count, es, rank,
+                lambda: ca.check(ca.all_reduce_radix_batch(send, recv, count, dt, ca.SUM, comm, k, b)), world))
+            fill_rank(rank, send)  # the metric's inputs back for the comparison lines
+        except Exception as e:  # recorded, never hidden: line_problems() flags a full line without a passing check
+            check = {"error": str(e)[:200]}
+        torch.cuda.empty_cache()
     allph = [None] * world
     dist.all_gather_object(allph, phases)
     phases_ms = {}
@@ -1213,11 +1257,13 @@ def bench_allreduce(args):
     # the context entries, so the deadline can only cost context (rank 0 runs it; the other ranks
     # wait at the barrier)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_collective(world, k, b, count, es, budget_s=deadline.t_end - time.time() - 30)
     dist.barrier()
-    compare = None if args.no_compare else compare_lines(args, ca, torch, dist, comm, send, recv, count, dt, k, b,
-                                                         world, dev, metric_sched, deadline)
+    compare = None
+    if args.full and not args.no_compare:
+        compare = compare_lines(args, ca, torch, dist, comm, send, recv, count, dt, k, b, world, dev, metric_sched,
+                                deadline)
     if rank == 0:
         line = {
             "metric": METRIC, "value": round(world * S * args.steps / el / 1e9, 2), "unit": "GB/s",
@@ -1261,8 +1307,11 @@ def bench_allreduce(args):
             "phase_transfer_ms": phases_ms,
             # RCCL's own view: ranks, GPUs and the transport of every connected pair (xgmi: all P2P)
             "rccl": rccl,
-            "result_check": check,
+            # --full: roofline, phase_transfer_ms, cpu_baseline, result_check and compare beside the metric
+            "full": bool(args.full),
         }
+        if check is not None:
+            line["result_check"] = check
         if cpu:
             line["gpu_vs_cpu"] = round(line["value"] / cpu["value"], 1)
         if compare:
@@ -1731,7 +1780,7 @@ def _main():
     if args.rank_trees:
         bench_rank_trees(args)
         return
-    cpu = None if args.no_cpu_baseline else cpu_baseline(args.cpu_seconds)
+    cpu = cpu_baseline(args.cpu_seconds) if args.full and not args.no_cpu_baseline else None
     bench_bucket(args, cpu)
 
 

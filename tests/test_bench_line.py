@@ -193,6 +193,54 @@ def test_n1_line_definitions_are_enforced():
     assert any("achieved" in p for p in bench.line_problems(line))
 
 
+def test_plain_line_needs_no_result_check_and_a_full_line_does():
+    """A run without --full says so ("full": false) and carries no result check; a --full line, and a line from
+    before the option (no "full" key), must carry a passing one."""
+    line = _nn_line()
+    line.pop("result_check")
+    assert any("result_check missing" in p for p in bench.line_problems(line))
+    line["full"] = True
+    assert any("result_check missing" in p for p in bench.line_problems(line))
+    line["full"] = False
+    line["roofline"] = line["cpu_baseline"] = None
+    line.pop("compare")
+    assert bench.line_problems(line) == []
+    line["result_check"] = {"ranks_bit_identical": False, "within_tolerance": True}
+    assert any("result_check failed" in p for p in bench.line_problems(line))
+    n1 = _n1_line()
+    n1["full"], n1["cpu_baseline"] = False, None
+    n1.pop("result_check", None)
+    assert bench.line_problems(n1) == []
+
+
+def test_full_and_dump_outputs_options():
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 3)
+    args = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert args.full is True and args.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float32_and_samples_a_large_output_the_same_way_twice(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    small = torch.arange(1000, dtype=torch.float32) * 0.5
+    bench.dump_outputs(torch, str(tmp_path / "a"), "acc", small)
+    got = np.load(tmp_path / "a" / "acc.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    bench.dump_outputs(torch, str(tmp_path / "a"), "half", small.to(torch.bfloat16))
+    assert np.load(tmp_path / "a" / "half.npy").dtype == np.float32
+    assert bench.DUMP_MAX_ELEMS * 4 <= 64 * 10**6  # one array per run, within 64 MB
+    # past the cap: a fixed sample of DUMP_MAX_ELEMS positions, sorted, the same from run to run
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1 << 10)
+    big = torch.arange(1 << 16, dtype=torch.float32)  # the value is the position
+    bench.dump_outputs(torch, str(tmp_path / "b"), "acc", big)
+    bench.dump_outputs(torch, str(tmp_path / "c"), "acc", big)
+    b, c = np.load(tmp_path / "b" / "acc.npy"), np.load(tmp_path / "c" / "acc.npy")
+    assert b.dtype == np.float32 and b.shape == (1 << 10,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) >= 0) and b.min() >= 0 and b.max() < (1 << 16) and len(np.unique(b)) > 900
+
+
 def test_committed_round5_lines_meet_the_definitions():
     """Every bench line a GPU run of this round committed (profiles/r05/**/bench*.json) obeys the same
     definitions."""

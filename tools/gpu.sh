@@ -47,7 +47,7 @@ for step in "$@"; do
   suite) CHR_GPU_SUITE_BUDGET_STRICT=1 run 1100 pytest_suite.txt $PYT --timeout 900 --durations=0 -m gpu tests/ ;;
   tests) run "${TEST_LIMIT:-900}" "pytest_${TAG:-tests}.txt" python -u -m pytest -x -v --timeout-method thread --timeout 170 -m gpu ${TESTS:?set TESTS} ;;
   smoke) run 300 smoke.txt python -c "import __graft_entry__ as g; g.smoke()" ;;
-  bench) run 300 bench.json python bench.py --steps 20 --warmup 5 ;;
+  bench) run 300 bench.json python bench.py --steps 20 --warmup 5 --full ;;
   bench200) run 300 bench200.json python bench.py --steps 200 --warmup 20 --no-cpu-baseline ;;
   prof) run 300 prof_bench.json rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -o run \
           -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline ;;
@@ -98,7 +98,7 @@ for step in "$@"; do
   launch)
     n=${N:-2}
     CHR_BENCH_VIRTUAL_HOSTS=1 CHR_BENCH_DEADLINE_S=${DEADLINE:-240} run 600 "bench_launch_n${n}.json" \
-      python bench.py --gpus "$n" --steps 3 --warmup 1 --count $((1 << 21)) ;;
+      python bench.py --gpus "$n" --steps 3 --warmup 1 --full --count $((1 << 21)) ;;
   launch8)  # the N=8 line at its real size (1 GiB per rank), 8 ranks sharing the one GPU over sockets: the
             # launcher and the deadline end to end (FLAT: AUTO's tuning over sockets would take minutes; a
             # heartbeat file keeps the call visibly alive while the socket-bound steps run)
@@ -106,12 +106,12 @@ for step in "$@"; do
     hb=$!
     trap 'kill $hb 2>/dev/null' EXIT
     CHR_BENCH_VIRTUAL_HOSTS=1 CHR_BENCH_DEADLINE_S=${DEADLINE:-150} CHR_SCHEDULE=${SCHED:-flat} run 700 "bench_launch_n8_1gib${SCHED:+_$SCHED}.json" \
-      python bench.py --gpus 8 --steps 2 --warmup 1
+      python bench.py --gpus 8 --steps 2 --warmup 1 --full
     kill $hb ;;
   rehearse)
     n=${N:-4}
     CHR_BENCH_VIRTUAL_HOSTS=1 run 600 "bench_n${n}_rehearsal.json" python -m torch.distributed.run --nnodes=1 \
-      --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29731 bench.py --gpus "$n" --steps 3 --warmup 1 \
+      --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29731 bench.py --gpus "$n" --steps 3 --warmup 1 --full \
       --count $((1 << 21)) ;;
   *) echo "unknown step $step"; exit 2 ;;
   esac

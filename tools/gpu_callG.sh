@@ -3,6 +3,6 @@
 set -u -o pipefail
 bash tools/gpu.sh bench200 sweep e2e || exit $?
 export HSA_ENABLE_IPC_MODE_LEGACY=0 TMPDIR=/tmp
-CHR_BENCH_VIRTUAL_HOSTS=1 CHR_SCHEDULE=flat CHR_BENCH_DEADLINE_S=200 timeout -k 10 600 python bench.py --gpus 4 \
+CHR_BENCH_VIRTUAL_HOSTS=1 CHR_SCHEDULE=flat CHR_BENCH_DEADLINE_S=200 timeout -k 10 600 python bench.py --gpus 4 --full \
   --count 268435456 > gpurun_out/bench_launch_n4_1gib_flat.json 2> gpurun_out/bench_launch_n4_1gib_flat.err || exit $?
 echo done
