@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "chr_internal.hpp"
 
@@ -114,29 +115,13 @@ template <> struct DTy<CHR_SHORT_INT> { using T = PairSI; };
 template <> struct DTy<CHR_C_FLOAT_COMPLEX> { using T = CplxF; };
 template <> struct DTy<CHR_C_DOUBLE_COMPLEX> { using T = CplxD; };
 
+// the predicates and the running-first op codes (kMaxSw ...): kernel_table.hpp
 template <int DT>
-constexpr bool is_pair_dt() { return DT >= CHR_FLOAT_INT && DT <= CHR_SHORT_INT; }
+constexpr bool is_pair_dt() { return is_pair_dtype(DT); }
 template <int DT>
-constexpr bool is_complex_dt() { return DT == CHR_C_FLOAT_COMPLEX || DT == CHR_C_DOUBLE_COMPLEX; }
-
+constexpr bool is_complex_dt() { return is_complex_dtype(DT); }
 template <int DT>
-constexpr bool is_float_dt() { return DT == CHR_FLOAT32 || DT == CHR_FLOAT64 || DT == CHR_BFLOAT16; }
-
-// Internal op codes for the running-value-first order of MPICH_do_reduce
-// (allreduce_recexch.cpp:147-186): each step is MPI_Reduce_local(running, next).  Integer SUM
-// and PROD are bitwise commutative (wrapping); MAX/MIN differ on ties such as -0/+0 and on NaN
-// compares, so they have their own codes.
-constexpr int kMaxSw = 16, kMinSw = 17;
-// SUM / PROD on the floating types are bitwise commutative except for one thing: when both operands are NaN, IEEE
-// 754 leaves open whose payload survives.  The reference's loop (inout = inout + in, MPICH on x86) keeps inout's;
-// gfx950 keeps the FIRST SOURCE OPERAND's (tools/nan_rule_probe.hip), and the compiler may commute a plain + or *
-// (`a + b` and `b + a` both compiled to a-first there).  So the kernels pin the order in the instruction
-// (add_keep / mul_keep above: the first argument's NaN survives), and the running-value-first order gets its own
-// codes, as MAX / MIN do: kSumSw / kProdSw keep the incoming operand's NaN (tests/test_gpu_nan_payloads.py).
-constexpr int kSumSw = 20, kProdSw = 21;
-// The same for MAXLOC / MINLOC on the pairs with a floating value: a NaN compare keeps inout, and a
-// tie keeps inout's value bits (-0 vs +0), so the operand order shows.
-constexpr int kMaxLocSw = 18, kMinLocSw = 19;
+constexpr bool is_float_dt() { return is_float_dtype(DT); }
 
 // x86 SSE arithmetic with its NaN rules written out, for the complex types (the oracle's orc_x86f / orc_x86d):
 // two NaNs -> the FIRST operand's, quieted; one NaN -> that NaN, quieted (sign and payload kept); an invalid
@@ -508,6 +493,50 @@ template <bool NT>
 __device__ __forceinline__ void st(u32x4* p, u32x4 v) {
     if constexpr (NT) __builtin_nontemporal_store(v, p);
     else *p = v;
+}
+
+// ---- host-side dispatch ------------------------------------------------------------------
+
+// Calls f(DT, OP) -- two std::integral_constants -- for the kernel (kdt, kop) if translation unit TU owns it
+// (kernel_tu in kernel_table.hpp); hipErrorInvalidValue for every other pair.  Only TU's own pairs are
+// instantiated, so each kernel is compiled into exactly one code object.
+template <int TU, int DT, typename F, size_t... J>
+inline hipError_t dispatch_kernel_op(int kop, F& f, std::index_sequence<J...>) {
+    hipError_t r = hipErrorInvalidValue;
+    auto one = [&](auto op) {
+        if constexpr (kernel_tu(is_tree_tu(TU), DT, decltype(op)::value) == TU) r = f(std::integral_constant<int, DT>{}, op);
+    };
+    (void)((kop == kKernelOps[J] && (one(std::integral_constant<int, kKernelOps[J]>{}), true)) || ...);
+    return r;
+}
+template <int TU, typename F, size_t... I>
+inline hipError_t dispatch_kernel_dt(int kdt, int kop, F& f, std::index_sequence<I...>) {
+    hipError_t r = hipErrorInvalidValue;
+    (void)((kdt == (int)I &&
+            (r = dispatch_kernel_op<TU, (int)I>(kop, f, std::make_index_sequence<kNumKernelOps>{}), true)) || ...);
+    return r;
+}
+template <int TU, typename F>
+inline hipError_t dispatch_kernel(int kdt, int kop, F f) {
+    return dispatch_kernel_dt<TU>(kdt, kop, f, std::make_index_sequence<kNumDtypes>{});
+}
+
+// How a call over `n` elements of `es` bytes splits into a scalar head, a body of 16-byte vectors and a scalar
+// tail.  congruent: `out` and every operand share one offset within 16 bytes, a multiple of the element size;
+// otherwise the whole call runs on the scalar kernel (head, nvec, tail are 0).
+struct AlignSplit {
+    bool congruent;
+    size_t head, nvec, tail;
+};
+inline AlignSplit align_split(const void* out, const void* const* operands, int nops, size_t n, size_t es) {
+    const uintptr_t mis = (uintptr_t)out & 15u;
+    bool congruent = (mis % es) == 0;
+    for (int j = 0; j < nops; ++j) congruent = congruent && (((uintptr_t)operands[j] & 15u) == mis);
+    if (!congruent) return {false, 0, 0, 0};
+    size_t head = mis ? (16 - mis) / es : 0;
+    if (head > n) head = n;
+    const size_t E = 16 / es, nvec = (n - head) / E;
+    return {true, head, nvec, n - head - nvec * E};
 }
 
 }  // namespace chr

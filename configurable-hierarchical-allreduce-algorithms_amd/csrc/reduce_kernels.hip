@@ -36,85 +36,6 @@
 
 namespace chr {
 
-size_t dtype_size(int dtype) {
-    switch (dtype) {
-    case CHR_FLOAT32: return 4;
-    case CHR_FLOAT64: return 8;
-    case CHR_INT32: return 4;
-    case CHR_BFLOAT16: return 2;
-    case CHR_INT8: case CHR_UINT8: return 1;
-    case CHR_INT16: case CHR_UINT16: return 2;
-    case CHR_UINT32: return 4;
-    case CHR_INT64: case CHR_UINT64: return 8;
-    // the pair and complex types: the C struct, i.e. MPI's extent (the element stride of a buffer)
-    case CHR_FLOAT_INT: case CHR_2INT: case CHR_SHORT_INT: case CHR_C_FLOAT_COMPLEX: return 8;
-    case CHR_DOUBLE_INT: case CHR_LONG_INT: case CHR_C_DOUBLE_COMPLEX: return 16;
-    default: return 0;
-    }
-}
-
-static bool is_pair_dtype(int dtype) { return dtype >= CHR_FLOAT_INT && dtype <= CHR_SHORT_INT; }
-static bool is_complex_dtype(int dtype) { return dtype == CHR_C_FLOAT_COMPLEX || dtype == CHR_C_DOUBLE_COMPLEX; }
-
-static bool is_float_dtype(int dtype) {
-    return dtype == CHR_FLOAT32 || dtype == CHR_FLOAT64 || dtype == CHR_BFLOAT16;
-}
-
-// MPI's predefined-op/type table as MPICH 3.3.2's MPI_Reduce_local applies it (probed): SUM/PROD/
-// MAX/MIN on every type, the logical ops on the integer types and on float/double (an MPICH
-// extension of the standard's table), the bitwise ops on the integer types.  bf16 is this
-// library's own type: arithmetic and MAX/MIN only.
-bool valid_dtype_op(int dtype, int op) {
-    if (!dtype_size(dtype)) return false;
-    // MPICH 3.3.2's table for the pair and complex types (oracle/ref_pairs_probe table,
-    // tests/golden/pairs_manifest.json): MAXLOC / MINLOC on the pairs only, SUM / PROD on complex only
-    if (is_pair_dtype(dtype)) return op == CHR_MAXLOC || op == CHR_MINLOC;
-    if (is_complex_dtype(dtype)) return op == CHR_SUM || op == CHR_PROD;
-    if (op == CHR_MAXLOC || op == CHR_MINLOC) return false;
-    if (op >= CHR_SUM && op <= CHR_MIN) return true;
-    if (op >= CHR_LAND && op <= CHR_LXOR) return dtype != CHR_BFLOAT16;
-    return op >= CHR_BAND && op <= CHR_BXOR && !is_float_dtype(dtype);
-}
-
-// The kernel instantiation that computes (dtype, op).  Signedness only matters to MAX/MIN:
-// wrapping SUM/PROD, the logical and the bitwise ops give the same bits on the unsigned type of
-// the same width (int32's kernels serve uint32 there).  running_first (MPICH_do_reduce order)
-// changes results only for floating types: MAX/MIN on ties of -0/+0 and NaN compares, SUM/PROD on
-// which NaN survives when two meet (kSumSw / kProdSw).
-void canon_op(int dtype, int op, bool running_first, int* kdt, int* kop) {
-    *kop = op;
-    if (is_pair_dtype(dtype) || is_complex_dtype(dtype)) {
-        *kdt = dtype;
-        if (running_first && (dtype == CHR_FLOAT_INT || dtype == CHR_DOUBLE_INT))  // ties of -0/+0, NaN
-            *kop = op == CHR_MAXLOC ? kMaxLocSw : op == CHR_MINLOC ? kMinLocSw : op;
-        if (running_first && is_complex_dtype(dtype))  // which NaN survives, per part (reduce_common.hpp apply)
-            *kop = op == CHR_SUM ? kSumSw : op == CHR_PROD ? kProdSw : op;
-        return;
-    }
-    if (is_float_dtype(dtype)) {
-        *kdt = dtype;
-        if (running_first && (op == CHR_MAX || op == CHR_MIN)) *kop = op == CHR_MAX ? kMaxSw : kMinSw;
-        if (running_first && (op == CHR_SUM || op == CHR_PROD)) *kop = op == CHR_SUM ? kSumSw : kProdSw;  // NaN payloads
-        return;
-    }
-    if (op == CHR_MAX || op == CHR_MIN) {
-        *kdt = dtype;
-        return;
-    }
-    switch (dtype_size(dtype)) {
-    case 1: *kdt = CHR_UINT8; break;
-    case 2: *kdt = CHR_UINT16; break;
-    case 4: *kdt = CHR_INT32; break;
-    default: *kdt = CHR_UINT64; break;
-    }
-}
-
-// kernel types compiled in this translation unit; the rest: reduce_int.hip
-static bool in_core_tu(int kdt, int kop) {
-    return (is_float_dtype(kdt) || kdt == CHR_INT32) && ((kop >= CHR_SUM && kop <= CHR_MIN) || kop == kMaxSw ||
-                                                         kop == kMinSw || kop == kSumSw || kop == kProdSw);
-}
-
 int& coresident_depth() {
     static thread_local int depth = 0;
     return depth;
@@ -166,53 +87,18 @@ ReduceTuning& reduce_tuning() {
 
 // ---- host launchers ----------------------------------------------------------------------
 
-template <int DT>
-static hipError_t launch_vec_dt(const VecArgs& a, int m, int op, hipStream_t s) {
-    switch (op) {
-    case CHR_SUM: return launch_vec_op<DT, CHR_SUM>(a, m, s);
-    case CHR_PROD: return launch_vec_op<DT, CHR_PROD>(a, m, s);
-    case CHR_MAX: return launch_vec_op<DT, CHR_MAX>(a, m, s);
-    case CHR_MIN: return launch_vec_op<DT, CHR_MIN>(a, m, s);
-    case kMaxSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_vec_op<DT, kMaxSw>(a, m, s);
-    case kMinSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_vec_op<DT, kMinSw>(a, m, s);
-    case kSumSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_vec_op<DT, kSumSw>(a, m, s);
-    case kProdSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_vec_op<DT, kProdSw>(a, m, s);
+// kdt/kop: the kernel type and op from canon_op.  Each call goes to the translation unit that owns its kernel
+// (kernel_table.hpp): this one's (kTuCore), reduce_int.hip's or reduce_pair.hip's.
+static hipError_t launch_vec(const VecArgs& a, int kdt, int kop, int m, hipStream_t s) {
+    kdt = vec_kernel_dt(kdt, kop);
+    switch (kernel_tu(false, kdt, kop)) {
+    case kTuCore: return launch_vec_tu<kTuCore>(a, kdt, kop, m, s);
+    case kTuInt: return launch_vec_int(a, kdt, kop, m, s);
+    case kTuPair: return launch_vec_pair(a, kdt, kop, m, s);
     default: return hipErrorInvalidValue;
     }
 }
 
-template <int DT>
-static hipError_t launch_scalar_dt(const ScalarArgs& a, int op, hipStream_t s) {
-    switch (op) {
-    case CHR_SUM: return launch_scalar_op<DT, CHR_SUM>(a, s);
-    case CHR_PROD: return launch_scalar_op<DT, CHR_PROD>(a, s);
-    case CHR_MAX: return launch_scalar_op<DT, CHR_MAX>(a, s);
-    case CHR_MIN: return launch_scalar_op<DT, CHR_MIN>(a, s);
-    case kMaxSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_scalar_op<DT, kMaxSw>(a, s);
-    case kMinSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_scalar_op<DT, kMinSw>(a, s);
-    case kSumSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_scalar_op<DT, kSumSw>(a, s);
-    case kProdSw:
-        if constexpr (DT == CHR_INT32) return hipErrorInvalidValue;
-        else return launch_scalar_op<DT, kProdSw>(a, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// kdt/kop: the kernel type and op from canon_op
 static hipError_t launch_scalar(void* out, const void* acc, const void* const* ins, int m, size_t n, int kdt,
                                 int kop, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -222,13 +108,10 @@ static hipError_t launch_scalar(void* out, const void* acc, const void* const* i
     a.m = m;
     a.n = n;
     for (int j = 0; j < m; ++j) a.ins[j] = ins[j];
-    if (is_pair_dtype(kdt) || is_complex_dtype(kdt)) return launch_scalar_pair(a, kdt, kop, s);
-    if (!in_core_tu(kdt, kop)) return launch_scalar_int(a, kdt, kop, s);
-    switch (kdt) {
-    case CHR_FLOAT32: return launch_scalar_dt<CHR_FLOAT32>(a, kop, s);
-    case CHR_FLOAT64: return launch_scalar_dt<CHR_FLOAT64>(a, kop, s);
-    case CHR_INT32: return launch_scalar_dt<CHR_INT32>(a, kop, s);
-    case CHR_BFLOAT16: return launch_scalar_dt<CHR_BFLOAT16>(a, kop, s);
+    switch (kernel_tu(false, kdt, kop)) {
+    case kTuCore: return launch_scalar_tu<kTuCore>(a, kdt, kop, s);
+    case kTuInt: return launch_scalar_int(a, kdt, kop, s);
+    case kTuPair: return launch_scalar_pair(a, kdt, kop, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -237,43 +120,25 @@ static hipError_t launch_scalar(void* out, const void* acc, const void* const* i
 static hipError_t launch_group(void* out, const void* acc, const void* const* ins, int m, size_t n, int dtype,
                                int op, hipStream_t s) {
     const size_t es = dtype_size(dtype);  // dtype, op: the kernel type and op (canon_op)
-    const uintptr_t mis = (uintptr_t)out & 15u;
-    bool congruent = ((uintptr_t)acc & 15u) == mis && (mis % es) == 0;
-    for (int j = 0; j < m; ++j) congruent = congruent && (((uintptr_t)ins[j] & 15u) == mis);
-    if (!congruent) return launch_scalar(out, acc, ins, m, n, dtype, op, s);
-    size_t head = mis ? (16 - mis) / es : 0;
-    if (head > n) head = n;
-    const size_t E = 16 / es;
-    const size_t nvec = (n - head) / E;
-    const size_t tail = n - head - nvec * E;
+    const void* operands[kMaxFanIn + 1] = {acc};
+    for (int j = 0; j < m; ++j) operands[j + 1] = ins[j];
+    const AlignSplit sp = align_split(out, operands, m + 1, n, es);
+    if (!sp.congruent) return launch_scalar(out, acc, ins, m, n, dtype, op, s);
     hipError_t err;
-    if (head && (err = launch_scalar(out, acc, ins, m, head, dtype, op, s)) != hipSuccess) return err;
-    if (nvec) {
+    if (sp.head && (err = launch_scalar(out, acc, ins, m, sp.head, dtype, op, s)) != hipSuccess) return err;
+    if (sp.nvec) {
         VecArgs a{};
-        a.out = (u32x4*)((char*)out + head * es);
-        a.acc = (const u32x4*)((const char*)acc + head * es);
-        for (int j = 0; j < m; ++j) a.ins[j] = (const u32x4*)((const char*)ins[j] + head * es);
-        a.nvec = nvec;
-        if (is_pair_dtype(dtype) || is_complex_dtype(dtype)) {
-            err = launch_vec_pair(a, dtype, op, m, s);
-        } else if (!in_core_tu(dtype, op)) {
-            err = launch_vec_int(a, dtype, op, m, s);
-        } else {
-            switch (dtype) {
-            case CHR_FLOAT32: err = launch_vec_dt<CHR_FLOAT32>(a, m, op, s); break;
-            case CHR_FLOAT64: err = launch_vec_dt<CHR_FLOAT64>(a, m, op, s); break;
-            case CHR_INT32: err = launch_vec_dt<CHR_INT32>(a, m, op, s); break;
-            case CHR_BFLOAT16: err = launch_vec_dt<CHR_BFLOAT16>(a, m, op, s); break;
-            default: err = hipErrorInvalidValue;
-            }
-        }
-        if (err != hipSuccess) return err;
+        a.out = (u32x4*)((char*)out + sp.head * es);
+        a.acc = (const u32x4*)((const char*)acc + sp.head * es);
+        for (int j = 0; j < m; ++j) a.ins[j] = (const u32x4*)((const char*)ins[j] + sp.head * es);
+        a.nvec = sp.nvec;
+        if ((err = launch_vec(a, dtype, op, m, s)) != hipSuccess) return err;
     }
-    if (tail) {
-        const size_t o = (head + nvec * E) * es;
+    if (sp.tail) {
+        const size_t o = (n - sp.tail) * es;
         const void* tins[kMaxFanIn];
         for (int j = 0; j < m; ++j) tins[j] = (const char*)ins[j] + o;
-        return launch_scalar((char*)out + o, (const char*)acc + o, tins, m, tail, dtype, op, s);
+        return launch_scalar((char*)out + o, (const char*)acc + o, tins, m, sp.tail, dtype, op, s);
     }
     return hipSuccess;
 }
@@ -283,7 +148,8 @@ hipError_t launch_reduce(void* out, const void* acc, const void* const* ins, int
     if (n == 0) return hipSuccess;
     if (!valid_dtype_op(dtype, op)) return hipErrorInvalidValue;
     const size_t es = dtype_size(dtype);
-    canon_op(dtype, op, running_first, &dtype, &op);
+    const KernelId k = canon_op(dtype, op, running_first);
+    dtype = k.dt, op = k.op;
     if (m == 0) {
         if (out == acc) return hipSuccess;
         return hipMemcpyAsync(out, acc, n * es, hipMemcpyDeviceToDevice, stream);

@@ -12,78 +12,11 @@
 
 namespace chr {
 
-template <int DT>
-static hipError_t vec_loc(const VecArgs& a, int op, int m, hipStream_t s) {
-    switch (op) {
-    case CHR_MAXLOC: return launch_vec_op<DT, CHR_MAXLOC>(a, m, s);
-    case CHR_MINLOC: return launch_vec_op<DT, CHR_MINLOC>(a, m, s);
-    case kMaxLocSw:
-        if constexpr (DT == CHR_FLOAT_INT || DT == CHR_DOUBLE_INT) return launch_vec_op<DT, kMaxLocSw>(a, m, s);
-        else return hipErrorInvalidValue;
-    case kMinLocSw:
-        if constexpr (DT == CHR_FLOAT_INT || DT == CHR_DOUBLE_INT) return launch_vec_op<DT, kMinLocSw>(a, m, s);
-        else return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int DT>
-static hipError_t vec_cplx(const VecArgs& a, int op, int m, hipStream_t s) {
-    if (op == CHR_SUM) return launch_vec_op<DT, CHR_SUM>(a, m, s);
-    if (op == CHR_PROD) return launch_vec_op<DT, CHR_PROD>(a, m, s);
-    if (op == kSumSw) return launch_vec_op<DT, kSumSw>(a, m, s);
-    if (op == kProdSw) return launch_vec_op<DT, kProdSw>(a, m, s);
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_vec_pair(const VecArgs& a, int kdt, int kop, int m, hipStream_t s) {
-    switch (kdt) {
-    case CHR_FLOAT_INT: return vec_loc<CHR_FLOAT_INT>(a, kop, m, s);
-    case CHR_DOUBLE_INT: return vec_loc<CHR_DOUBLE_INT>(a, kop, m, s);
-    case CHR_LONG_INT: return vec_loc<CHR_LONG_INT>(a, kop, m, s);
-    case CHR_2INT: return vec_loc<CHR_2INT>(a, kop, m, s);
-    case CHR_SHORT_INT: return vec_loc<CHR_SHORT_INT>(a, kop, m, s);
-    case CHR_C_FLOAT_COMPLEX: return vec_cplx<CHR_C_FLOAT_COMPLEX>(a, kop, m, s);
-    case CHR_C_DOUBLE_COMPLEX: return vec_cplx<CHR_C_DOUBLE_COMPLEX>(a, kop, m, s);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_vec_tu<kTuPair>(a, kdt, kop, m, s);
 }
-
-template <int DT>
-static hipError_t scalar_loc(const ScalarArgs& a, int op, hipStream_t s) {
-    switch (op) {
-    case CHR_MAXLOC: return launch_scalar_op<DT, CHR_MAXLOC>(a, s);
-    case CHR_MINLOC: return launch_scalar_op<DT, CHR_MINLOC>(a, s);
-    case kMaxLocSw:
-        if constexpr (DT == CHR_FLOAT_INT || DT == CHR_DOUBLE_INT) return launch_scalar_op<DT, kMaxLocSw>(a, s);
-        else return hipErrorInvalidValue;
-    case kMinLocSw:
-        if constexpr (DT == CHR_FLOAT_INT || DT == CHR_DOUBLE_INT) return launch_scalar_op<DT, kMinLocSw>(a, s);
-        else return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int DT>
-static hipError_t scalar_cplx(const ScalarArgs& a, int op, hipStream_t s) {
-    if (op == CHR_SUM) return launch_scalar_op<DT, CHR_SUM>(a, s);
-    if (op == CHR_PROD) return launch_scalar_op<DT, CHR_PROD>(a, s);
-    if (op == kSumSw) return launch_scalar_op<DT, kSumSw>(a, s);
-    if (op == kProdSw) return launch_scalar_op<DT, kProdSw>(a, s);
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_scalar_pair(const ScalarArgs& a, int kdt, int kop, hipStream_t s) {
-    switch (kdt) {
-    case CHR_FLOAT_INT: return scalar_loc<CHR_FLOAT_INT>(a, kop, s);
-    case CHR_DOUBLE_INT: return scalar_loc<CHR_DOUBLE_INT>(a, kop, s);
-    case CHR_LONG_INT: return scalar_loc<CHR_LONG_INT>(a, kop, s);
-    case CHR_2INT: return scalar_loc<CHR_2INT>(a, kop, s);
-    case CHR_SHORT_INT: return scalar_loc<CHR_SHORT_INT>(a, kop, s);
-    case CHR_C_FLOAT_COMPLEX: return scalar_cplx<CHR_C_FLOAT_COMPLEX>(a, kop, s);
-    case CHR_C_DOUBLE_COMPLEX: return scalar_cplx<CHR_C_DOUBLE_COMPLEX>(a, kop, s);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_scalar_tu<kTuPair>(a, kdt, kop, s);
 }
 
 }  // namespace chr

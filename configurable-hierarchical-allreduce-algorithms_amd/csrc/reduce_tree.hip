@@ -5,28 +5,15 @@
 
 namespace chr {
 
-template <int DT>
-static hipError_t launch_tree_dt(const TreeArgs& a, const TreeScalarArgs* sa, int op, hipStream_t s) {
-    switch (op) {
-    case CHR_SUM: return launch_tree_op<DT, CHR_SUM>(a, sa, s);
-    case CHR_PROD: return launch_tree_op<DT, CHR_PROD>(a, sa, s);
-    case CHR_MAX: return launch_tree_op<DT, CHR_MAX>(a, sa, s);
-    case CHR_MIN: return launch_tree_op<DT, CHR_MIN>(a, sa, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// dtype, op: the kernel type and op (canon_op)
-static hipError_t launch_tree_any(const TreeArgs& a, const TreeScalarArgs* sa, int dtype, int op, hipStream_t s) {
-    if (dtype >= CHR_FLOAT_INT && dtype <= CHR_C_DOUBLE_COMPLEX) return launch_tree_pair(a, sa, dtype, op, s);
-    const bool core = (dtype == CHR_FLOAT32 || dtype == CHR_FLOAT64 || dtype == CHR_BFLOAT16 || dtype == CHR_INT32) &&
-                      op <= CHR_MIN;
-    if (!core) return launch_tree_int(a, sa, dtype, op, s);
-    switch (dtype) {
-    case CHR_FLOAT32: return launch_tree_dt<CHR_FLOAT32>(a, sa, op, s);
-    case CHR_FLOAT64: return launch_tree_dt<CHR_FLOAT64>(a, sa, op, s);
-    case CHR_INT32: return launch_tree_dt<CHR_INT32>(a, sa, op, s);
-    case CHR_BFLOAT16: return launch_tree_dt<CHR_BFLOAT16>(a, sa, op, s);
+// The tree kernel of (kdt, kop) -- from canon_op -- in the translation unit that owns it: the scalar kernel if `sa`
+// (heads, tails and calls that are not 16-byte congruent), else the vector kernel.
+static hipError_t launch_tree_any(const TreeArgs& a, const TreeScalarArgs* sa, int kdt, int kop, hipStream_t s) {
+    if (!sa) kdt = vec_kernel_dt(kdt, kop);
+    switch (kernel_tu(true, kdt, kop)) {
+    case kTuTree: return launch_tree_tu<kTuTree>(a, sa, kdt, kop, s);
+    case kTuTreeIntNarrow: return launch_tree_int_narrow(a, sa, kdt, kop, s);
+    case kTuTreeIntWide: return launch_tree_int_wide(a, sa, kdt, kop, s);
+    case kTuTreePair: return launch_tree_pair(a, sa, kdt, kop, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -56,9 +43,9 @@ bool tree_program_ok(int nl, const uint8_t* comb, const uint8_t* swaps, uint32_t
 hipError_t launch_reduce_tree_multi(const TreeJob* jobs, int njobs, int dtype, int op, hipStream_t stream) {
     if (!valid_dtype_op(dtype, op)) return hipErrorInvalidValue;
     const size_t es = dtype_size(dtype);
-    const int dtype0 = dtype, op0 = op;       // the caller's (type, op), for the bucket kernel
-    canon_op(dtype, op, false, &dtype, &op);  // the per-combine swap bits carry the operand order
-    const size_t E = 16 / es;
+    const int dtype0 = dtype, op0 = op;            // the caller's (type, op), for the bucket kernel
+    const KernelId k = canon_op(dtype, op, false);  // the per-combine swap bits carry the operand order
+    dtype = k.dt, op = k.op;
     TreeArgs pend[kMaxLeaves + 1] = {};  // pending vector segments, by leaf count
     auto flush = [&](int nl) -> hipError_t {
         TreeArgs& a = pend[nl];
@@ -95,9 +82,8 @@ hipError_t launch_reduce_tree_multi(const TreeJob* jobs, int njobs, int dtype, i
                 continue;
             }
         }
-        const uintptr_t mis = (uintptr_t)jb.out & 15u;
-        bool congruent = (mis % es) == 0;
-        for (int j = 0; j < nl; ++j) congruent = congruent && (((uintptr_t)jb.leaves[j] & 15u) == mis);
+        const AlignSplit sp = align_split(jb.out, jb.leaves, nl, jb.n, es);
+        const size_t head = sp.head, nvec = sp.nvec;
         auto scalar = [&](size_t off, size_t cnt) -> hipError_t {
             if (!cnt) return hipSuccess;
             TreeScalarArgs sa{};
@@ -111,15 +97,11 @@ hipError_t launch_reduce_tree_multi(const TreeJob* jobs, int njobs, int dtype, i
             return launch_tree_any(dummy, &sa, dtype, op, stream);
         };
         hipError_t err;
-        if (!congruent) {
+        if (!sp.congruent) {
             if ((err = scalar(0, jb.n)) != hipSuccess) return err;
             continue;
         }
-        size_t head = mis ? (16 - mis) / es : 0;
-        if (head > jb.n) head = jb.n;
-        const size_t nvec = (jb.n - head) / E;
-        const size_t tail = jb.n - head - nvec * E;
-        if ((err = scalar(0, head)) != hipSuccess || (err = scalar(head + nvec * E, tail)) != hipSuccess) return err;
+        if ((err = scalar(0, head)) != hipSuccess || (err = scalar(jb.n - sp.tail, sp.tail)) != hipSuccess) return err;
         const size_t cap = reduce_tuning().max_launch_vec;
         const size_t seg_cap = cap && cap < kMaxSegVec ? cap : kMaxSegVec;
         for (size_t off = 0; off < nvec; off += seg_cap) {  // pieces of at most 1 GiB per operand

@@ -1,6 +1,6 @@
 // reduce_tree.hpp -- the fused expression-tree kernel (templates), shared by reduce_tree.hip
-// (floating types, int32 arithmetic) and reduce_tree_int.hip (the other integer types, logical
-// and bitwise ops).
+// (floating types, int32 arithmetic), reduce_tree_int_narrow.hip / reduce_tree_int_wide.hip (the other
+// integer types, logical and bitwise ops) and reduce_tree_pair.hip (pair and complex types).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -482,9 +482,20 @@ inline hipError_t launch_tree_op(const TreeArgs& a, const TreeScalarArgs* sa, hi
     }
 }
 
-// The integer kernel types of reduce_tree_int.hip (kdt/kop from canon_op).
-hipError_t launch_tree_int(const TreeArgs& a, const TreeScalarArgs* sa, int kdt, int kop, hipStream_t s);
-// The pair (MAXLOC / MINLOC) and complex (SUM / PROD) types of reduce_tree_pair.hip.
+// The tree kernels of (kdt, kop) that translation unit TU owns (kernel_table.hpp): the scalar kernel if `sa`, else
+// the vector kernel (kdt through vec_kernel_dt).  Each unit defines its entry point with this.
+template <int TU>
+inline hipError_t launch_tree_tu(const TreeArgs& a, const TreeScalarArgs* sa, int kdt, int kop, hipStream_t s) {
+    return dispatch_kernel<TU>(kdt, kop, [&](auto dt, auto op) {
+        constexpr int DT = decltype(dt)::value, OP = decltype(op)::value;
+        if constexpr (vec_kernel_dt(DT, OP) != DT) return sa ? launch_tree_scalar_op<DT, OP>(*sa, s) : hipErrorInvalidValue;
+        else return launch_tree_op<DT, OP>(a, sa, s);
+    });
+}
+
+// kTuTree's: reduce_tree.hip, which routes every launch to its unit
+hipError_t launch_tree_int_narrow(const TreeArgs& a, const TreeScalarArgs* sa, int kdt, int kop, hipStream_t s);
+hipError_t launch_tree_int_wide(const TreeArgs& a, const TreeScalarArgs* sa, int kdt, int kop, hipStream_t s);
 hipError_t launch_tree_pair(const TreeArgs& a, const TreeScalarArgs* sa, int kdt, int kop, hipStream_t s);
 
 

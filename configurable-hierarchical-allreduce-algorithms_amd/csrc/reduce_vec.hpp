@@ -243,12 +243,27 @@ inline hipError_t launch_scalar_op(const ScalarArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// The vector and scalar bucket kernels of (kdt, kop) -- from canon_op; for the vector kernel through vec_kernel_dt
+// too -- that translation unit TU owns (kernel_table.hpp).  Each unit defines its pair of entry points with these.
+template <int TU>
+inline hipError_t launch_vec_tu(const VecArgs& a, int kdt, int kop, int m, hipStream_t s) {
+    return dispatch_kernel<TU>(kdt, kop, [&](auto dt, auto op) {
+        constexpr int DT = decltype(dt)::value, OP = decltype(op)::value;
+        if constexpr (vec_kernel_dt(DT, OP) != DT) return hipErrorInvalidValue;  // scalar kernel only
+        else return launch_vec_op<DT, OP>(a, m, s);
+    });
+}
+template <int TU>
+inline hipError_t launch_scalar_tu(const ScalarArgs& a, int kdt, int kop, hipStream_t s) {
+    return dispatch_kernel<TU>(kdt, kop, [&](auto dt, auto op) {
+        return launch_scalar_op<decltype(dt)::value, decltype(op)::value>(a, s);
+    });
+}
 
-// Launches for the integer kernel types of reduce_int.hip (kdt/kop from canon_op).
-hipError_t launch_vec_int(const VecArgs& a, int kdt, int kop, int m, hipStream_t s);
+// kTuCore's: reduce_kernels.hip, which routes every call to its unit
+hipError_t launch_vec_int(const VecArgs& a, int kdt, int kop, int m, hipStream_t s);  // reduce_int.hip
 hipError_t launch_scalar_int(const ScalarArgs& a, int kdt, int kop, hipStream_t s);
-// The pair (MAXLOC / MINLOC) and complex (SUM / PROD) types of reduce_pair.hip.
-hipError_t launch_vec_pair(const VecArgs& a, int kdt, int kop, int m, hipStream_t s);
+hipError_t launch_vec_pair(const VecArgs& a, int kdt, int kop, int m, hipStream_t s);  // reduce_pair.hip
 hipError_t launch_scalar_pair(const ScalarArgs& a, int kdt, int kop, hipStream_t s);
 
 }  // namespace chr

@@ -122,8 +122,8 @@ def test_large_nt_path(gu):
 @pytest.mark.parametrize("op", ["sum", "prod", "max", "min", "land", "lor", "lxor", "band", "bor", "bxor"])
 def test_integer_types_and_logical_bitwise_ops(gu, dtype, op):
     """The whole-tree kernel on every MPI integer type and op the reference's generic
-    MPI_Datatype x MPI_Op admits (reduce_tree_int.hip), C4's tree and a depth-4 one, plus a
-    misaligned (scalar) pass."""
+    MPI_Datatype x MPI_Op admits (reduce_tree_int_narrow.hip / reduce_tree_int_wide.hip), C4's tree and a
+    depth-4 one, plus a misaligned (scalar) pass."""
     pat = {"land": po.PAT_SPARSE, "lor": po.PAT_TIES, "lxor": po.PAT_TIES}.get(op, po.PAT_UNIFORM)
     if op == "prod" and dtype == "i32":
         return  # int32 arithmetic is the core instantiation, covered above

@@ -5,6 +5,7 @@ three waves per SIMD, and rcclGenericKernel's wave needs ~288 of the SIMD's 512 
 may take at most 72 (granules of 8).  Above that the RCCL-sized kernel waits for the reduction launch to drain
 (U = 2 trees at 82-90: admission 4 -> 170 us, profiles/r05/cores_u/; bf16 trees at 80 after the NaN-payload fix:
 median admission 29-48 -> 5.5-14 us once back at 61, profiles/r05/cores_ab_bf16/)."""
+import collections
 import os
 import re
 import shutil
@@ -52,6 +53,16 @@ def test_every_kernel_found_and_none_uses_scratch(res):
     assert len(res) > 2000
     scratch = {n: r["scratch"] for n, r in res.items() if r["scratch"]}
     assert not scratch, f"kernels with a private segment: {sorted(scratch)[:5]}"
+
+
+def test_each_kernel_is_compiled_once():
+    """The (type, op) table (csrc/kernel_table.hpp) gives every kernel to exactly one translation unit: no name in
+    two code objects, and the set the library has shipped since round 6."""
+    objs = kr.code_objects(_lib.LIB_PATH)
+    count = collections.Counter(n for obj in objs for n in obj)
+    twice = sorted(n for n, c in count.items() if c > 1)
+    assert not twice, f"kernels in more than one code object: {twice[:5]}"
+    assert len(count) == 2837
 
 
 def test_streaming_kernels_leave_rccl_its_registers(res):

@@ -47,7 +47,8 @@ def _bundles(fat):
         pos = i + 1
 
 
-def kernel_resources(lib=DEFAULT_LIB):
+def code_objects(lib=DEFAULT_LIB):
+    """One {kernel: {vgpr, agpr, scratch, lds}} per gfx950 code object, i.e. per HIP translation unit."""
     with tempfile.TemporaryDirectory() as tmp:
         fat_path = os.path.join(tmp, "fat.bin")
         subprocess.run([OBJCOPY, "--dump-section", f".hip_fatbin={fat_path}", lib, os.path.join(tmp, "stripped")],
@@ -55,7 +56,7 @@ def kernel_resources(lib=DEFAULT_LIB):
         fat = open(fat_path, "rb").read()
         if fat.startswith(b"CCOB"):
             raise RuntimeError("compressed offload bundle: build without --offload-compress")
-        res = {}
+        objs = []
         for k, (o, sz) in enumerate(_bundles(fat)):
             co = os.path.join(tmp, f"co{k}.o")
             with open(co, "wb") as f:
@@ -64,11 +65,18 @@ def kernel_resources(lib=DEFAULT_LIB):
             text = notes[notes.index("---"):]
             text = text[:text.index("\n...") + 4] if "\n..." in text else text
             meta = yaml.safe_load(text)
-            for kern in meta["amdhsa.kernels"]:
-                res[kern[".name"]] = {"vgpr": kern[".vgpr_count"], "agpr": kern.get(".agpr_count", 0),
-                                      "scratch": kern[".private_segment_fixed_size"],
-                                      "lds": kern[".group_segment_fixed_size"]}
-        return res
+            objs.append({kern[".name"]: {"vgpr": kern[".vgpr_count"], "agpr": kern.get(".agpr_count", 0),
+                                         "scratch": kern[".private_segment_fixed_size"],
+                                         "lds": kern[".group_segment_fixed_size"]}
+                         for kern in meta["amdhsa.kernels"]})
+        return objs
+
+
+def kernel_resources(lib=DEFAULT_LIB):
+    res = {}
+    for obj in code_objects(lib):
+        res.update(obj)
+    return res
 
 
 def alloc_vgprs(r):
