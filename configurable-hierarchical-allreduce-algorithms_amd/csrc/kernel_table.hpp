@@ -23,8 +23,10 @@ constexpr int kMaxSw = 16, kMinSw = 17;
 // gets its own codes, as MAX / MIN do: kSumSw / kProdSw keep the incoming operand's NaN
 // (tests/test_gpu_nan_payloads.py).
 constexpr int kSumSw = 20, kProdSw = 21;
-// The same for MAXLOC / MINLOC on the pairs with a floating value: a NaN compare keeps inout, and a
-// tie keeps inout's value bits (-0 vs +0), so the operand order shows.
+// The same for MAXLOC / MINLOC on every pair type but 2INT: a tie keeps inout's words and takes only the lower
+// index, so the operand order shows in the value bits of the floating pairs (-0 vs +0; a NaN compare keeps inout
+// too) and in the padding bytes of DOUBLE_INT, LONG_INT and SHORT_INT (MPICH's loop never touches a.value's
+// padding on a tie; tests/domain_util.py fills it).  2INT has no padding and ties are bitwise equal.
 constexpr int kMaxLocSw = 18, kMinLocSw = 19;
 // every op code a kernel is instantiated for: chr_op's, then the running-first codes
 constexpr int kKernelOps[] = {CHR_SUM,  CHR_PROD,   CHR_MAX,    CHR_MIN, CHR_LAND, CHR_LOR,   CHR_LXOR,  CHR_BAND, CHR_BOR,
@@ -50,6 +52,7 @@ constexpr size_t dtype_size(int dtype) {
 }
 
 constexpr bool is_pair_dtype(int dtype) { return dtype >= CHR_FLOAT_INT && dtype <= CHR_SHORT_INT; }
+constexpr bool pair_order_shows(int dtype) { return is_pair_dtype(dtype) && dtype != CHR_2INT; }  // kMaxLocSw
 constexpr bool is_complex_dtype(int dtype) { return dtype == CHR_C_FLOAT_COMPLEX || dtype == CHR_C_DOUBLE_COMPLEX; }
 constexpr bool is_float_dtype(int dtype) {
     return dtype == CHR_FLOAT32 || dtype == CHR_FLOAT64 || dtype == CHR_BFLOAT16;
@@ -84,11 +87,11 @@ struct KernelId {
 // The kernel instantiation that computes (dtype, op).  Signedness only matters to MAX/MIN:
 // wrapping SUM/PROD, the logical and the bitwise ops give the same bits on the unsigned type of
 // the same width (int32's kernels serve uint32 there).  running_first (MPICH_do_reduce order)
-// changes results only for floating types: MAX/MIN on ties of -0/+0 and NaN compares, SUM/PROD on
-// which NaN survives when two meet (kSumSw / kProdSw).
+// changes results only for floating types -- MAX/MIN on ties of -0/+0 and NaN compares, SUM/PROD on
+// which NaN survives when two meet (kSumSw / kProdSw) -- and for MAXLOC/MINLOC ties (kMaxLocSw).
 constexpr KernelId canon_op(int dtype, int op, bool running_first) {
     if (is_pair_dtype(dtype) || is_complex_dtype(dtype)) {
-        if (running_first && (dtype == CHR_FLOAT_INT || dtype == CHR_DOUBLE_INT))  // ties of -0/+0, NaN
+        if (running_first && pair_order_shows(dtype))  // ties: -0/+0, NaN compares, padding bytes
             return {dtype, op == CHR_MAXLOC ? kMaxLocSw : op == CHR_MINLOC ? kMinLocSw : op};
         if (running_first && is_complex_dtype(dtype))  // which NaN survives, per part (reduce_common.hpp apply)
             return {dtype, op == CHR_SUM ? kSumSw : op == CHR_PROD ? kProdSw : op};
@@ -112,7 +115,7 @@ constexpr KernelId canon_op(int dtype, int op, bool running_first) {
 constexpr bool kernel_exists(int kdt, int kop) {
     if (is_pair_dtype(kdt))
         return kop == CHR_MAXLOC || kop == CHR_MINLOC ||
-               ((kdt == CHR_FLOAT_INT || kdt == CHR_DOUBLE_INT) && (kop == kMaxLocSw || kop == kMinLocSw));
+               (pair_order_shows(kdt) && (kop == kMaxLocSw || kop == kMinLocSw));
     if (is_complex_dtype(kdt)) return kop == CHR_SUM || kop == CHR_PROD || kop == kSumSw || kop == kProdSw;
     if (is_float_dtype(kdt)) return is_arith_op(kop) || is_arith_sw_op(kop) || (is_logic_op(kop) && kdt != CHR_BFLOAT16);
     switch (kdt) {

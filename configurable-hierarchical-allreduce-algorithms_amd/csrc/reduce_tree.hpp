@@ -62,12 +62,13 @@ struct TreeArgs {
 constexpr size_t kMaxSegVec = (size_t)1 << 26;
 
 // Whether MPI_Reduce_local(running, next) can differ bitwise from MPI_Reduce_local(next, running):
-// MAX / MIN on floating types and MAXLOC / MINLOC on floating-valued pairs (ties, -0 / +0, NaN), and SUM / PROD on
-// the floating and the complex types when two NaNs meet (whose payload survives: kSumSw in reduce_common.hpp).
+// MAX / MIN on floating types (ties, -0 / +0, NaN), MAXLOC / MINLOC on every pair type but 2INT (a tie keeps inout's
+// words: the value bits of the floating pairs, the padding bytes of LONG_INT and SHORT_INT; pair_order_shows), and SUM /
+// PROD on the floating and the complex types when two NaNs meet (whose payload survives: kSumSw in reduce_common.hpp).
 template <int DT, int OP>
 constexpr bool order_sensitive() {
     return (is_float_dt<DT>() && (OP == CHR_MAX || OP == CHR_MIN || OP == CHR_SUM || OP == CHR_PROD)) ||
-           ((DT == CHR_FLOAT_INT || DT == CHR_DOUBLE_INT) && (OP == CHR_MAXLOC || OP == CHR_MINLOC)) ||
+           (pair_order_shows(DT) && (OP == CHR_MAXLOC || OP == CHR_MINLOC)) ||
            (is_complex_dt<DT>() && (OP == CHR_SUM || OP == CHR_PROD));
 }
 
