@@ -112,19 +112,37 @@ def reduce_multi(out, acc, ins, count, datatype, op, stream=None):
     return lib().chr_reduce_multi(_addr(out), _addr(acc), arr, len(ins), count, datatype, op, _stream(stream))
 
 
-def op_create(launcher, commute=False, ctx=None):
+# op code -> (launcher, tree): the library holds the launchers' addresses until op_free, so the objects they came
+# from (a CFUNCTYPE wrapper would otherwise be collected) live as long
+_OP_LAUNCHERS = {}
+
+
+def _fn_addr(fn):
+    return fn if isinstance(fn, int) else ctypes.cast(fn, ctypes.c_void_p).value
+
+
+def op_create(launcher, commute=False, ctx=None, tree=None):
     """A user-defined op (chr_op_create, MPI_Op_create's analogue): `launcher` is the address of a chr_user_reduce_fn
     -- the caller's own device code, e.g. built with include/chiara_user_op.hpp -- as an int or a ctypes function.
-    Returns the op code for every chr_reduce_* call and CHiArA's collectives."""
-    addr = ctypes.cast(launcher, ctypes.c_void_p).value if not isinstance(launcher, int) else launcher
+    `tree`, optional and given the same way, is a chr_user_tree_fn that evaluates whole expression trees in one pass
+    (chr_op_create_tree; CHR_DEFINE_USER_TREE).  Returns the op code for every chr_reduce_* call and CHiArA's
+    collectives.  Both launcher objects are kept alive until op_free."""
     op = ctypes.c_int(0)
-    check(lib().chr_op_create(addr, ctx, int(bool(commute)), ctypes.byref(op)), "chr_op_create")
+    if tree is None:
+        check(lib().chr_op_create(_fn_addr(launcher), ctx, int(bool(commute)), ctypes.byref(op)), "chr_op_create")
+    else:
+        check(lib().chr_op_create_tree(_fn_addr(launcher), _fn_addr(tree), ctx, int(bool(commute)), ctypes.byref(op)),
+              "chr_op_create_tree")
+    _OP_LAUNCHERS[op.value] = (launcher, tree)
     return op.value
 
 
 def op_free(op):
     """Release a user-defined op (chr_op_free); its code may be handed out again."""
-    return lib().chr_op_free(op)
+    rc = lib().chr_op_free(op)
+    if rc == SUCCESS:
+        _OP_LAUNCHERS.pop(op, None)
+    return rc
 
 
 def fill(buf, count, datatype, pattern, seed, rank, count_for_seq=None, stream=None):

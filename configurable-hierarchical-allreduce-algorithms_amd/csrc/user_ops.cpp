@@ -5,8 +5,10 @@
 // arithmetic is the caller's own device code: chr_op_create registers a host launcher that enqueues it on the stream
 // the library passes (include/chiara.h chr_user_reduce_fn; include/chiara_user_op.hpp builds one from a device
 // functor).  Folds go to the launcher as they are; an expression tree (the flat schedules' one-pass evaluation,
-// k_reduce_tree for the predefined ops) is evaluated fold by fold in its post-order program, intermediate values in
-// stream-ordered scratch.  Nothing runs on the host.
+// k_reduce_tree for the predefined ops) goes whole to the op's tree launcher where it registered one
+// (chr_op_create_tree: one HBM pass, inner nodes in registers) and is otherwise, or when that launcher declines,
+// evaluated fold by fold in its post-order program, intermediate values in stream-ordered scratch.  Nothing runs on
+// the host.
 #include "user_ops.hpp"
 
 #include <mutex>
@@ -20,6 +22,7 @@ namespace {
 
 struct UserOp {
     chr_user_reduce_fn fn = nullptr;
+    chr_user_tree_fn tree_fn = nullptr;  // optional: whole trees in one pass (chr_op_create_tree)
     void* ctx = nullptr;
     int commute = 0;
     bool live = false;
@@ -114,8 +117,51 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
     if (!rc && st.size() == 1 && st[0].p != out)
         rc = hip_status(hipMemcpyAsync(out, st[0].p, bytes, hipMemcpyDeviceToDevice, s));
     for (void* q : slot)
-        if (q) (void)hipFreeAsync(q, s);
+        if (q) {
+            const int e = hip_status(hipFreeAsync(q, s));
+            if (!rc) rc = e;
+        }
     return rc;
+}
+
+// Every job with n > 0 and two or more leaves goes to the op's tree launcher in one call, with the residency cap a
+// streaming launch of the library's own would take on this thread (stream_wg_cap: kCoresidentWgPerCu beside RCCL, else
+// none).  A launcher that declines has enqueued nothing (chiara.h): those jobs, like the 1-leaf ones and every job of
+// an op without a tree launcher, are evaluated fold by fold.
+int user_trees(const UserOp& u, const TreeJob* jobs, int njobs, int dtype, hipStream_t s) {
+    bool handed = false;
+    if (u.tree_fn) {
+        std::vector<chr_user_tree> ts;
+        for (int t = 0; t < njobs; ++t) {
+            const TreeJob& jb = jobs[t];
+            if (jb.n == 0 || jb.nl < 2) continue;
+            chr_user_tree ut{};
+            ut.out = jb.out;
+            ut.nleaves = jb.nl;
+            ut.n = jb.n;
+            int nc = 0;
+            for (int j = 0; j < jb.nl; ++j) {
+                ut.leaves[j] = jb.leaves[j];
+                ut.comb[j] = jb.comb[j];
+                nc += jb.comb[j];
+            }
+            for (int c = 0; c < nc && c < 8; ++c) ut.swaps[c] = jb.swaps && jb.swaps[c] ? 1 : 0;
+            ts.push_back(ut);
+        }
+        if (!ts.empty()) {
+            const int cap = coresident_depth() > 0 ? kCoresidentWgPerCu : 0;
+            if (u.tree_fn(ts.data(), (int)ts.size(), (chr_dtype)dtype, cap, s, u.ctx) == 0) {
+                if (int rc = hip_status(hipGetLastError())) return rc;
+                handed = true;
+            }
+        }
+    }
+    for (int t = 0; t < njobs; ++t) {
+        const TreeJob& jb = jobs[t];
+        if (jb.n == 0 || (handed && jb.nl >= 2)) continue;
+        if (int rc = user_tree(u, jb.out, jb.leaves, jb.nl, jb.comb, jb.swaps, jb.n, dtype, s)) return rc;
+    }
+    return CHR_SUCCESS;
 }
 
 }  // namespace
@@ -148,19 +194,22 @@ int reduce_tree_any(void* out, const void* const* leaves, int nl, const uint8_t*
     if (!is_user_op(op)) return hip_status(launch_reduce_tree(out, leaves, nl, comb, swaps, n, dtype, op, s));
     if (!lookup(op, &u)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
-    return user_tree(u, out, leaves, nl, comb, swaps, n, dtype, s);
+    if (nl < 1 || nl > 8) return CHR_ERR_INVALID_ARG;
+    TreeJob jb{};
+    jb.out = out;
+    for (int j = 0; j < nl; ++j) jb.leaves[j] = leaves[j];
+    jb.nl = nl;
+    jb.comb = comb;
+    jb.swaps = swaps;
+    jb.n = n;
+    return user_trees(u, &jb, 1, dtype, s);
 }
 
 int reduce_tree_multi_any(const TreeJob* jobs, int njobs, int dtype, int op, hipStream_t s) {
     UserOp u;
     if (!is_user_op(op)) return hip_status(launch_reduce_tree_multi(jobs, njobs, dtype, op, s));
     if (!lookup(op, &u)) return CHR_ERR_INVALID_ARG;
-    for (int t = 0; t < njobs; ++t)
-        if (jobs[t].n)
-            if (int rc = user_tree(u, jobs[t].out, jobs[t].leaves, jobs[t].nl, jobs[t].comb, jobs[t].swaps, jobs[t].n,
-                                   dtype, s))
-                return rc;
-    return CHR_SUCCESS;
+    return user_trees(u, jobs, njobs, dtype, s);
 }
 
 }  // namespace chr
@@ -168,12 +217,17 @@ int reduce_tree_multi_any(const TreeJob* jobs, int njobs, int dtype, int op, hip
 extern "C" {
 
 int chr_op_create(chr_user_reduce_fn fn, void* ctx, int commute, chr_op* op) {
+    return chr_op_create_tree(fn, nullptr, ctx, commute, op);
+}
+
+int chr_op_create_tree(chr_user_reduce_fn fn, chr_user_tree_fn tree_fn, void* ctx, int commute, chr_op* op) {
     if (!fn || !op) return CHR_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(chr::g_mu);
     for (int i = 0; i < chr::kMaxUserOps; ++i) {
         chr::UserOp& u = chr::g_ops[i];
         if (u.live) continue;
         u.fn = fn;
+        u.tree_fn = tree_fn;
         u.ctx = ctx;
         u.commute = commute != 0;
         u.live = true;

@@ -23,7 +23,9 @@ bool op_commutative(int op);
 bool valid_any(int dtype, int op);
 
 // The reductions: chr_result codes.  reduce_any is MPI_Reduce_local chained over ins (launch_reduce's contract);
-// reduce_tree_any evaluates one post-order program (launch_reduce_tree's); reduce_tree_multi_any a batch of them.
+// reduce_tree_any evaluates one post-order program (launch_reduce_tree's); reduce_tree_multi_any a batch of them.  A
+// user op's trees go to its tree launcher in one call per batch (chr_op_create_tree), fold by fold through its fold
+// launcher when it has none or the launcher declines.
 int reduce_any(void* out, const void* acc, const void* const* ins, int m, size_t n, int dtype, int op, hipStream_t s,
                bool running_first = false);
 int reduce_tree_any(void* out, const void* const* leaves, int nl, const uint8_t* comb, const uint8_t* swaps, size_t n,

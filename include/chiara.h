@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CHR_ABI_VERSION 11 /* 11: user-defined ops (chr_op_create); 10: chr_comm_get_overlap; 9: chr_comm_info; 8: the stand-alone phase collectives (chr_intra_reduce_scatter_radix_batch, ...) */
+#define CHR_ABI_VERSION 11 /* 11: user-defined ops (chr_op_create; added since, no signature changed: chr_op_create_tree, CHR_OP_USER_LAST); 10: chr_comm_get_overlap; 9: chr_comm_info; 8: the stand-alone phase collectives (chr_intra_reduce_scatter_radix_batch, ...) */
 
 /* Element types.  The reference is generic over MPI_Datatype (all_reduce_radix_batch.cpp:202-204,
  * sizes from MPI_Type_size at :234-277); these are the MPI predefined types MPICH's
@@ -64,7 +64,8 @@ typedef enum {
     CHR_SUM = 0, CHR_PROD = 1, CHR_MAX = 2, CHR_MIN = 3,
     CHR_LAND = 4, CHR_LOR = 5, CHR_LXOR = 6,  /* MPI_LAND, MPI_LOR, MPI_LXOR */
     CHR_BAND = 7, CHR_BOR = 8, CHR_BXOR = 9,  /* MPI_BAND, MPI_BOR, MPI_BXOR */
-    CHR_MAXLOC = 10, CHR_MINLOC = 11          /* MPI_MAXLOC, MPI_MINLOC */
+    CHR_MAXLOC = 10, CHR_MINLOC = 11,         /* MPI_MAXLOC, MPI_MINLOC */
+    CHR_OP_USER_LAST = 127                    /* the last user-op code: chr_op_create's 64..127 lie inside the enum's range */
 } chr_op;
 
 typedef enum {
@@ -109,6 +110,42 @@ typedef int (*chr_user_reduce_fn)(void* out, const void* acc, const void* const*
                                   int running_first, hipStream_t stream, void* ctx);
 int chr_op_create(chr_user_reduce_fn fn, void* ctx, int commute, chr_op* op);
 int chr_op_free(chr_op op);
+
+/* ---- user-defined ops, whole expression trees in one pass ------------------------------
+ * The flat schedules evaluate each chunk as one expression tree (chr_reduce_tree below).  For a predefined op that
+ * is one HBM pass: every leaf read once, the root written once.  Through `fn` alone a user op's tree runs fold by
+ * fold, inner nodes in stream-ordered scratch (C4's 8-leaf tree: three launcher calls and 13 units of traffic
+ * against 9).  chr_op_create_tree registers, beside `fn`, a launcher that evaluates whole trees itself
+ * (include/chiara_user_op.hpp builds one from the same device functor: CHR_DEFINE_USER_TREE).  `fn` stays required
+ * -- folds, 1-leaf trees and declined calls go through it -- and a NULL `tree_fn` makes the call chr_op_create.  The
+ * op comes from the same 64 codes and chr_op_free releases it.
+ *
+ * One chr_user_tree is one chr_reduce_tree program over `n` elements: push leaves[j], then comb[j] combines, each
+ * popping the top `top` and folding it into the running value `run` below it; with x o y = fn(invec = x, inoutvec =
+ * y), combine c computes run = top o run, or with swaps[c] set run = run o top (MPICH_do_reduce's order).  At most 8
+ * leaves, stack depth 4.  `out` may alias a leaf (same element offset).  A call hands over every tree of one batch
+ * (the trees of one pipeline slice, or of one chr_reduce_tree_batch call); they are independent of each other.
+ *
+ * `wg_per_cu` is the residency the library asks for: 12 while the call runs beside RCCL's kernels on a multi-rank
+ * communicator, 0 (the launcher's own choice) otherwise.  Beside a streaming reduction resident on every CU, RCCL's
+ * send/receive kernel (256 threads at ~288 VGPRs per wave, 20-38 KB of LDS) was admitted within microseconds only
+ * when the reduction held at most 12 workgroups per CU; at 14, 16 or uncapped it waited for the reduction's launch
+ * to drain.  Honour it as the library's kernels do: dynamic LDS of (LDS per CU) / wg_per_cu bytes per workgroup.
+ *
+ * Return 0 once every tree of the call is enqueued on `stream`.  Anything else declines the call, and then NOTHING
+ * may have been enqueued: the library evaluates those trees fold by fold through `fn`, whose verdict alone can
+ * become CHR_ERR_UNSUPPORTED.  Declining is not an error. */
+typedef struct {
+    void* out;                 /* may alias a leaf at the same element offset */
+    const void* leaves[8];
+    int nleaves;               /* 2..8 (the library handles 1-leaf trees itself) */
+    unsigned char comb[8];     /* chr_reduce_tree's post-order program */
+    unsigned char swaps[8];    /* one per combine, program order; [7] unused */
+    size_t n;                  /* elements, > 0 */
+} chr_user_tree;
+typedef int (*chr_user_tree_fn)(const chr_user_tree* trees, int ntrees, chr_dtype dtype, int wg_per_cu,
+                                hipStream_t stream, void* ctx);
+int chr_op_create_tree(chr_user_reduce_fn fn, chr_user_tree_fn tree_fn, void* ctx, int commute, chr_op* op);
 
 /* ---- kernel boundary: replaces MPI_Reduce_local --------------------------------------
  * Reference call sites (MPI_Reduce_local(in, inout, count, datatype, op)):

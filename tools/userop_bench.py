@@ -1,17 +1,41 @@
-"""User-defined op (chr_op_create) against the predefined SUM on the same shapes: the fold (MPI_Reduce_local, 64 MiB
-buckets, m = 1 and 3, HBM-cold rotation) and an 8-virtual-rank C4-shaped allreduce (k = 4, b = 4, the flat
-schedule's 8-leaf trees, evaluated for a user op as chained folds, user_ops.cpp user_tree).  One JSON line.
-Measurement tool; the user op is tests/userop/halfadd_op.hip (one mul + one add per element, like SUM's one add)."""
+"""User-defined op (chr_op_create) against the predefined SUM on the same shapes.  One JSON line (and --out FILE).
+
+ * the fold (MPI_Reduce_local, 64 MiB buckets, m = 1 and 3, HBM-cold rotation);
+ * an 8-virtual-rank C4-shaped allreduce (k = 4, b = 4, the flat schedule's 8-leaf trees), 128 MiB per rank, in
+   three variants: SUM (k_reduce_tree), the user op registered folds-only (chr_op_create: every tree as chained
+   folds, user_ops.cpp user_tree) and the same op registered with its one-pass tree launcher (chr_op_create_tree,
+   include/chiara_user_op.hpp k_tree);
+ * the tree API alone (chr_reduce_tree, C4's 8-leaf program) at 16 MiB and 64 MiB per leaf over an HBM-cold rotation
+   of ~2.25 GiB, the same three variants, as the fraction of 8 TB/s at 9 units of traffic (8 leaves read, the root
+   written: what the one-pass kernels move; the folds move 13) -- and the tree launcher called directly at the
+   residency caps 12, 16 and 64 workgroups per CU (64 is above the wave-slot limit: uncapped), the A/B behind
+   CHR_USER_TREE_WG_PER_CU; and the same 8-leaf tree at 1 MiB per leaf on one cache-resident set.
+ * --ab NAME=LIB.so adds the one-pass rows of another build of tests/userop/halfadd_tree_op.hip (make -C tests/userop -f tree_op.mk ab:
+   its flags plus e.g. -DCHR_USER_TREE_NT=0 -DCHR_USER_TREE_XCD_RUN_KIB=0): the A/B of the kernel's policy knobs.
+
+The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
+shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
++ one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
+import argparse
 import ctypes
 import json
 import os
 import sys
+import time
 
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "configurable-hierarchical-allreduce-algorithms_amd"))
 import chiara_amd as ca  # noqa: E402
+
+C4_COMB, C4_SWAPS = [0, 1, 1, 1, 0, 1, 1, 2], [0] * 7
+HBM_PEAK = 8e12
+
+
+class UserTree(ctypes.Structure):  # chiara.h chr_user_tree
+    _fields_ = [("out", ctypes.c_void_p), ("leaves", ctypes.c_void_p * 8), ("nleaves", ctypes.c_int),
+                ("comb", ctypes.c_ubyte * 8), ("swaps", ctypes.c_ubyte * 8), ("n", ctypes.c_size_t)]
 
 
 def timed(fn, reps):
@@ -27,13 +51,10 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def main():
+def fold_rows(out, dev, stream):
     lib = ctypes.CDLL(os.environ.get("CHR_USEROP_SO", os.path.join(REPO, "tests", "userop", "libhalfadd_op.so")))
-    out_tag = os.environ.get("CHR_USEROP_SO", "")
+    out["lib"] = os.path.basename(os.environ.get("CHR_USEROP_SO", "")) or "libhalfadd_op.so"
     half = ca.op_create(ctypes.cast(lib.chr_test_halfadd, ctypes.c_void_p).value)
-    dev = torch.device("cuda:0")
-    stream = torch.cuda.current_stream(dev)
-    out = {"tool": "tools/userop_bench.py", "lib": os.path.basename(out_tag) or "libhalfadd_op.so"}
     n = 16 << 20  # 64 MiB fp32
     for m in (1, 3):
         sets = max(1, (2 << 30) // ((m + 1) * 4 * n))
@@ -45,24 +66,111 @@ def main():
             ms = timed(go, 60)
             out[f"fold_m{m}_{name}_GBps"] = round((m + 2) * 4 * n / (ms * 1e-3) / 1e9, 1)
         del bufs
-    nr, cnt = 8, 8 * (4 << 20)  # 128 MiB per rank
+    ca.op_free(half)
+
+
+def c4_rows(rounds, variants):
+    """8-virtual-rank C4-shaped allreduce, 128 MiB per rank: ms per call, per round and variant."""
+    dev = torch.device("cuda:0")
+    nr, cnt = 8, 8 * (4 << 20)
     g = ca.LocalGroup(nr, 0)
     sends = [torch.rand(cnt, device=dev) for _ in range(nr)]
     recvs = [torch.empty(cnt, device=dev) for _ in range(nr)]
-    import time
-
-    for name, op in (("sum", ca.SUM), ("user", half)):
-        for _ in range(2):
-            ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, ca.FLOAT32, op, 4, 4))
-        torch.cuda.synchronize()  # device-wide: the group's own stream included
-        t0 = time.perf_counter()
-        for _ in range(5):
-            ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, ca.FLOAT32, op, 4, 4))
-        torch.cuda.synchronize()
-        out[f"localgroup8_k4b4_128MiB_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+    rows = []
+    for _ in range(rounds):
+        row = {}
+        for name, op in variants:
+            for _ in range(2):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, ca.FLOAT32, op, 4, 4))
+            torch.cuda.synchronize()  # device-wide: the group's own stream included
+            t0 = time.perf_counter()
+            for _ in range(5):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, ca.FLOAT32, op, 4, 4))
+            torch.cuda.synchronize()
+            row[f"localgroup8_k4b4_128MiB_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+        rows.append(row)
     g.destroy()
-    ca.op_free(half)
-    print(json.dumps(out))
+    return rows
+
+
+def tree_rows(rounds, variants, tree_fn, stream):
+    """chr_reduce_tree on C4's 8-leaf program, HBM-cold: fraction of 8 TB/s at 9 units, per round and variant."""
+    dev = torch.device("cuda:0")
+    rows = [{} for _ in range(rounds)]
+    for mib in (1, 16, 64):
+        n = mib << 18  # fp32 elements per leaf
+        # 1 MiB leaves: one set, cache-resident (what a small collective's trees see); else the HBM-cold rotation
+        sets = 1 if mib == 1 else int(2.25 * (1 << 30)) // (9 * 4 * n)
+        bufs = [[torch.rand(n, device=dev) for _ in range(9)] for _ in range(sets)]
+        trees = []
+        for s in bufs:
+            t = UserTree()
+            t.out = s[8].data_ptr()
+            for j in range(8):
+                t.leaves[j] = s[j].data_ptr()
+                t.comb[j] = C4_COMB[j]
+            t.nleaves, t.n = 8, n
+            trees.append(t)
+        reps = {1: 400, 16: 240, 64: 80}[mib]
+        for r in range(rounds):
+            for name, op in variants:
+                def go(i, op=op):
+                    s = bufs[i % sets]
+                    ca.check(ca.reduce_tree(s[8], s[:8], C4_COMB, C4_SWAPS, n, ca.FLOAT32, op, stream))
+                ms = timed(go, reps)
+                rows[r][f"tree8_{mib}MiB_{name}_frac"] = round(9 * 4 * n / (ms * 1e-3) / HBM_PEAK, 4)
+            for cap in (12, 16, 64):
+                def go(i, cap=cap):
+                    if tree_fn(ctypes.byref(trees[i % sets]), 1, ca.FLOAT32, cap, stream.cuda_stream, None) != 0:
+                        raise RuntimeError("tree launcher declined")
+                ms = timed(go, reps)
+                rows[r][f"tree8_{mib}MiB_launcher_cap{cap}_frac"] = round(9 * 4 * n / (ms * 1e-3) / HBM_PEAK, 4)
+        del bufs, trees
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--no-folds", action="store_true", help="skip the fold rows")
+    ap.add_argument("--ab", action="append", default=[], metavar="NAME=LIB.so",
+                    help="a build of tests/userop/halfadd_tree_op.hip with other knobs (-DCHR_USER_TREE_NT=1, "
+                         "-DCHR_USER_TREE_XCD_RUN_KIB=512, ...): its one-pass rows as user_tree_NAME")
+    ap.add_argument("--out", help="also write the JSON here")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream(dev)
+    out = {"tool": "tools/userop_bench.py", "tree_lib": "libhalfadd_tree_op.so"}
+    if not a.no_folds:
+        fold_rows(out, dev, stream)
+    tlib = ctypes.CDLL(os.path.join(REPO, "tests", "userop", "libhalfadd_tree_op.so"))
+    fold = ctypes.cast(tlib.chr_test_halfadd, ctypes.c_void_p).value
+    tree_fn = tlib.chr_test_halfadd_tree
+    tree_fn.argtypes = [ctypes.POINTER(UserTree), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                        ctypes.c_void_p]
+    tree_fn.restype = ctypes.c_int
+    folds_only = ca.op_create(fold)
+    one_pass = ca.op_create(fold, tree=ctypes.cast(tree_fn, ctypes.c_void_p).value)
+    variants = [("sum", ca.SUM), ("user_folds", folds_only), ("user_tree", one_pass)]
+    ab_libs = []
+    for spec in a.ab:
+        name, path = spec.split("=", 1)
+        ab = ctypes.CDLL(os.path.abspath(path))
+        ab_libs.append(ab)
+        variants.append((f"user_tree_{name}", ca.op_create(ctypes.cast(ab.chr_test_halfadd, ctypes.c_void_p).value,
+                                                           tree=ctypes.cast(ab.chr_test_halfadd_tree, ctypes.c_void_p).value)))
+    out["ab"] = a.ab
+    c4 = c4_rows(a.rounds, variants)
+    tr = tree_rows(a.rounds, variants, tree_fn, stream)
+    out["rounds"] = [dict(c, **t) for c, t in zip(c4, tr)]
+    for _, op in variants[1:]:
+        ca.op_free(op)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
