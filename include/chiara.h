@@ -159,7 +159,10 @@ int chr_reduce_local(const void* in, void* inout, size_t n, chr_dtype dtype, chr
 /* Fused form of the k-1 (phase 1) or nnodes-1 (phase 2) consecutive Reduce_local calls
  * that target one region: out = (...((acc (op) ins[0]) (op) ins[1]) ...) (op) ins[m-1],
  * left to right, rounding after every step exactly as the sequential calls do
- * (all_reduce_radix_batch.cpp:343-364, :523-530).  `out` may alias `acc`. m >= 0. */
+ * (all_reduce_radix_batch.cpp:343-364, :523-530).  `out` may alias `acc`. m >= 0.
+ * The call writes exactly the n elements at `out` and nothing else: never an ins[j], never `acc`
+ * when it is distinct from `out`, no byte before `out` or past out + n (also for m > 8, where
+ * the later groups continue from `out`; pinned by tests/test_gpu_footprint.py). */
 int chr_reduce_multi(void* out, const void* acc, const void* const* ins, int m, size_t n,
                      chr_dtype dtype, chr_op op, hipStream_t stream);
 /* chr_reduce_multi with flags.  CHR_REDUCE_RUNNING_FIRST: the running value is the FIRST
@@ -185,7 +188,8 @@ int chr_reduce_multi_ex(void* out, const void* acc, const void* const* ins, int 
  * in program order) MPI_Reduce_local(below, in) (MPICH_do_reduce order).  The program must
  * leave exactly one value: sum(comb) == nleaves-1, comb[0] == 0.  Limits: 1 <= nleaves <= 8,
  * stack depth <= 4 (CHR_ERR_UNSUPPORTED otherwise).  `out` may alias a leaf at the same
- * element offset.  swaps may be NULL (all zero). */
+ * element offset.  swaps may be NULL (all zero).  The call writes exactly the n elements at `out`:
+ * every leaf other than the output is left as it was, and so is every byte around `out`. */
 int chr_reduce_tree(void* out, const void* const* leaves, int nleaves, const unsigned char* comb,
                     const unsigned char* swaps, size_t n, chr_dtype dtype, chr_op op,
                     hipStream_t stream);
@@ -194,7 +198,8 @@ int chr_reduce_tree(void* out, const void* const* leaves, int nleaves, const uns
  * a pipeline slice): tree t writes outs[t] from leaves[t*nleaves .. t*nleaves+nleaves-1] with the
  * program comb[t*nleaves ..] / swaps[t*(nleaves-1) ..] (swaps may be NULL).  Trees must not write
  * what another tree of the batch reads or writes (an in-place root over its own leaf is fine).
- * Bit-identical to ntrees chr_reduce_tree calls. */
+ * Bit-identical to ntrees chr_reduce_tree calls, and with the same footprint: exactly n elements
+ * at each outs[t], so trees whose outputs (or leaves) lie back to back never touch each other's. */
 int chr_reduce_tree_batch(void* const* outs, const void* const* leaves, int ntrees, int nleaves,
                           const unsigned char* comb, const unsigned char* swaps, size_t n,
                           chr_dtype dtype, chr_op op, hipStream_t stream);
@@ -343,7 +348,13 @@ long chr_comm_profile_phases(chr_comm* comm, char* buf, size_t len, int reset);
  * send/recv may be device pointers (device-resident path) or host pointers (staged
  * through HBM: the reference's host-memory-in / host-memory-out contract).  The call
  * returns once the result is in `recv` (stream synchronised).  Scratch is owned by the
- * communicator and reused across calls (the reference mallocs 2x the buffer per call). */
+ * communicator and reused across calls (the reference mallocs 2x the buffer per call).
+ * `send` is read only: no collective of this header ever writes it (no plan has a local op, a
+ * receive or an allgather region in the send buffer: tools/plan_fuzz.cpp).  A call writes exactly
+ * the result's elements at `recv` -- count for an allreduce, recvcount for a reduce-scatter,
+ * nranks * sendcount for an allgather -- and no byte before or after them.  Under CHR_IN_PLACE
+ * the reduce-scatters also use the rest of the nranks * recvcount input elements at `recv` as
+ * working space (unspecified afterwards, as in MPI) and nothing past them. */
 int chr_allreduce_radix_batch(const void* send, void* recv, size_t count, chr_dtype dtype,
                               chr_op op, chr_comm* comm, int k, int b);
 int chr_reduce_scatter_radix_batch(const void* send, void* recv, size_t recvcount,

@@ -1,5 +1,6 @@
 """Register and scratch budget of the one-pass user-op tree kernels (include/chiara_user_op.hpp k_tree), read from the
-test code object tests/userop/libhalfadd_tree_op.so (no GPU).
+test code object tests/userop/libhalfadd_tree_op.so (no GPU).  build() makes that file; where it is missing -- a tests/
+directory put in place after the build -- the fixture makes it the same way.
 
 The kernels are compiled into the caller's code object, so the library's own resource test does not see them.  Beside
 RCCL they run at 12 one-wave workgroups per CU like the library's trees, where a wave may take at
@@ -7,6 +8,7 @@ most 72 VGPRs (tests/test_kernel_resources.py); and an interpreter that indexed 
 show as a private segment."""
 import os
 import re
+import subprocess
 import sys
 
 import pytest
@@ -24,6 +26,10 @@ TYPES = {"f": "f32", "d": "f64", "i": "i32"}
 
 @pytest.fixture(scope="module")
 def res():
+    if not os.path.exists(TREE_SO):  # a tests/ directory put in place after build(): make it the way build() does
+        made = subprocess.run(["make", "-s", "-C", os.path.dirname(TREE_SO), "-f", "tree_op.mk"], capture_output=True,
+                              text=True, timeout=900)
+        assert made.returncode == 0, made.stdout[-2000:] + made.stderr[-2000:]
     assert os.path.exists(TREE_SO), f"{TREE_SO} missing: make -C tests/userop -f tree_op.mk (__graft_entry__.build())"
     return kr.kernel_resources(TREE_SO)
 

@@ -1,8 +1,11 @@
 // plan_fuzz.cpp -- host-only sweep of the schedule compiler under AddressSanitizer / UBSan.
 // Builds every rank's plan for every (mode, n, k, b, count, slices, schedule) in a wide grid,
 // checks the plans pair up (every send has a matching receive in the same step with the same
-// size) and that every buffer reference stays inside its declared buffer, and describes each
-// plan (exercising the printer).  Run by tests/test_plan_fuzz.py:
+// size), that every buffer reference stays inside its declared buffer and that no plan ever writes
+// the send buffer (no local op's dst, no receive, no allgather region is BUF_SEND, in `pre` or in
+// any step: the collectives take `const void* sendbuf`; plans do not know about CHR_IN_PLACE, the
+// executor aliases SEND to RECV, so the rule holds for every plan), and describes each plan
+// (exercising the printer).  Run by tests/test_plan_fuzz.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -Iinclude -I<pkg>/csrc tools/plan_fuzz.cpp <pkg>/csrc/schedule.cpp -o /tmp/plan_fuzz
 #include <cstdio>
@@ -39,6 +42,9 @@ static bool op_in_bounds(const Plan& p, const LocalOp& op) {
         if (!in_bounds(p, x, op.count)) return false;
     return true;
 }
+
+// A plan reads BUF_SEND and never writes it.
+static bool writes_send(const LocalOp& op) { return op.dst.buf == BUF_SEND; }
 
 int main(int argc, char** argv) {
     const int max_n = argc > 1 ? std::atoi(argv[1]) : 16;  // the CPU test runs a reduced grid
@@ -91,18 +97,25 @@ int main(int argc, char** argv) {
                                         for (const Xfer& x : st.recvs) {
                                             rcv[{x.peer, r}].push_back(x.count);
                                             if (!in_bounds(P[r], x.ref, x.count)) fail("recv bounds", mode, n, k, b, count, sched);
+                                            if (x.ref.buf == BUF_SEND) fail("recv writes SEND", mode, n, k, b, count, sched);
                                         }
-                                        for (const Coll& c : st.allgathers)
+                                        for (const Coll& c : st.allgathers) {
                                             if (!in_bounds(P[r], c.ref, c.count * (uint64_t)n))
                                                 fail("allgather bounds", mode, n, k, b, count, sched);
-                                        for (const LocalOp& op : st.post)
+                                            if (c.ref.buf == BUF_SEND) fail("allgather writes SEND", mode, n, k, b, count, sched);
+                                        }
+                                        for (const LocalOp& op : st.post) {
                                             if (!op_in_bounds(P[r], op)) fail("local op bounds", mode, n, k, b, count, sched);
+                                            if (writes_send(op)) fail("local op writes SEND", mode, n, k, b, count, sched);
+                                        }
                                     }
                                     if (snd != rcv) fail("unmatched messages", mode, n, k, b, count, sched);
                                 }
                                 for (const Plan& p : P)
-                                    for (const LocalOp& op : p.pre)
+                                    for (const LocalOp& op : p.pre) {
                                         if (!op_in_bounds(p, op)) fail("pre op bounds", mode, n, k, b, count, sched);
+                                        if (writes_send(op)) fail("pre op writes SEND", mode, n, k, b, count, sched);
+                                    }
                             }
             }
     std::printf("{\"plans\": %ld, \"failures\": %d}\n", plans, g_bad);
