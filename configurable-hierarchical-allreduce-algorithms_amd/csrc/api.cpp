@@ -37,11 +37,6 @@ const char* chr_error_string(int code) {
     }
 }
 
-static int status(hipError_t e) {
-    if (e == hipSuccess) return CHR_SUCCESS;
-    return e == hipErrorOutOfMemory ? CHR_ERR_OUT_OF_MEMORY : CHR_ERR_HIP;
-}
-
 int chr_reduce_local(const void* in, void* inout, size_t n, chr_dtype dtype, chr_op op, hipStream_t stream) {
     if (!chr::valid_any(dtype, op)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
@@ -52,12 +47,7 @@ int chr_reduce_local(const void* in, void* inout, size_t n, chr_dtype dtype, chr
 
 int chr_reduce_multi(void* out, const void* acc, const void* const* ins, int m, size_t n, chr_dtype dtype, chr_op op,
                      hipStream_t stream) {
-    if (!chr::valid_any(dtype, op) || m < 0) return CHR_ERR_INVALID_ARG;
-    if (n == 0) return CHR_SUCCESS;
-    if (!out || !acc || (m > 0 && !ins)) return CHR_ERR_INVALID_ARG;
-    for (int j = 0; j < m; ++j)
-        if (!ins[j]) return CHR_ERR_INVALID_ARG;
-    return chr::reduce_any(out, acc, ins, m, n, dtype, op, stream);
+    return chr_reduce_multi_ex(out, acc, ins, m, n, dtype, op, 0, stream);
 }
 
 int chr_reduce_multi_ex(void* out, const void* acc, const void* const* ins, int m, size_t n, chr_dtype dtype,
@@ -85,7 +75,8 @@ int chr_reduce_tree(void* out, const void* const* leaves, int nleaves, const uns
 int chr_reduce_tree_batch(void* const* outs, const void* const* leaves, int ntrees, int nleaves,
                           const unsigned char* comb, const unsigned char* swaps, size_t n, chr_dtype dtype, chr_op op,
                           hipStream_t stream) {
-    if (!chr::valid_any(dtype, op) || ntrees < 0 || nleaves < 1 || nleaves > 8) return CHR_ERR_INVALID_ARG;
+    if (!chr::valid_any(dtype, op) || ntrees < 0 || nleaves < 1 || nleaves > chr::kTreeMaxLeaves)
+        return CHR_ERR_INVALID_ARG;
     if (ntrees > 0 && (!outs || !leaves || !comb)) return CHR_ERR_INVALID_ARG;
     std::vector<chr::TreeJob> jobs((size_t)ntrees);
     for (int t = 0; t < ntrees; ++t) {
@@ -113,7 +104,7 @@ int chr_fill(void* buf, size_t n, chr_dtype dtype, int pattern, uint64_t seed, i
     if (!chr::dtype_size(dtype) || (pattern < 0 || pattern > 3)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
     if (!buf) return CHR_ERR_INVALID_ARG;
-    return status(chr::launch_fill(buf, n, dtype, pattern, seed, rank, count_for_seq, stream));
+    return chr::hip_code(chr::launch_fill(buf, n, dtype, pattern, seed, rank, count_for_seq, stream));
 }
 
 long chr_plan_describe(chr_mode mode, int nranks, int rank, int k, int b, size_t count, int slices, char* buf,

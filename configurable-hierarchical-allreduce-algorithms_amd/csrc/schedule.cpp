@@ -2,7 +2,7 @@
 // and the block-major ACC layout.  Line citations are to
 // Fugaku_experiments/Allreduce/all_reduce_radix_batch.cpp (the reduce-scatter file is
 // line-for-line identical through phase 2).
-#include "schedule.hpp"
+#include "plan_util.hpp"
 
 #include <functional>
 #include <tuple>
@@ -627,12 +627,6 @@ static Plan build_plan_impl(Mode mode, int n, int me, int k_in, int b, uint64_t 
 // are folded from there into `dst` in one pass.  Same association, same bits.
 static constexpr int kPlanFanIn = 8;
 
-static bool may_alias(const Ref& a, uint64_t na, const Ref& b, uint64_t nb) {
-    const bool io = (a.buf == BUF_SEND && b.buf == BUF_RECV) || (a.buf == BUF_RECV && b.buf == BUF_SEND);
-    if (io) return true;  // in place: SEND is RECV (offsets differ for allgather / reduce-scatter)
-    return a.buf == b.buf && a.off < b.off + nb && b.off < a.off + na;
-}
-
 static void split_wide_reductions(Plan& p) {
     const uint64_t scratch = p.stage_elems;
     uint64_t need = 0;
@@ -665,42 +659,7 @@ static void split_wide_reductions(Plan& p) {
 }
 
 // Dependencies for two-stream execution (transfers on the comm stream, local ops on the
-// compute stream).  Regions are compared in one address space for SEND and RECV (they are the
-// same memory under MPI_IN_PLACE; a false conflict only costs overlap, never correctness).
-struct Region {
-    uint8_t buf;
-    uint64_t lo, hi;
-};
-static uint8_t space(uint8_t b) { return b == BUF_SEND ? (uint8_t)BUF_RECV : b; }
-static bool overlap(const Region& a, const Region& b) {
-    return space(a.buf) == space(b.buf) && a.lo < b.hi && b.lo < a.hi;
-}
-static void op_regions(const LocalOp& op, std::vector<Region>* rd, std::vector<Region>* wr) {
-    if (op.kind == L_COPY2D) {
-        for (uint64_t r = 0; r < op.rows; ++r) {
-            rd->push_back({op.acc.buf, op.acc.off + r * op.spitch, op.acc.off + r * op.spitch + op.count});
-            wr->push_back({op.dst.buf, op.dst.off + r * op.dpitch, op.dst.off + r * op.dpitch + op.count});
-        }
-        return;
-    }
-    rd->push_back({op.acc.buf, op.acc.off, op.acc.off + op.count});
-    for (const Ref& x : op.ins) rd->push_back({x.buf, x.off, x.off + op.count});
-    wr->push_back({op.dst.buf, op.dst.off, op.dst.off + op.count});
-}
-static bool conflict(const std::vector<Region>& wr_a, const std::vector<Region>& rd_a, const std::vector<Region>& rd_b,
-                     const std::vector<Region>& wr_b) {
-    for (const Region& a : wr_a) {
-        for (const Region& b : rd_b)
-            if (overlap(a, b)) return true;  // RAW
-        for (const Region& b : wr_b)
-            if (overlap(a, b)) return true;  // WAW
-    }
-    for (const Region& a : rd_a)
-        for (const Region& b : wr_b)
-            if (overlap(a, b)) return true;  // WAR
-    return false;
-}
-
+// compute stream), on plan_util.hpp's regions: one address space for SEND and RECV.
 static void analyze_deps(Plan& p) {
     const size_t ns = p.steps.size();
     std::vector<std::vector<Region>> prd(ns), pwr(ns);
@@ -788,8 +747,7 @@ static Plan build_plan_impl(Mode mode, int n, int me, int k_in, int b, uint64_t 
     p.recv_elems = mode == MODE_ALLREDUCE ? g.total : recvcount;
     p.acc_elems = g.total;
     if (g.total == 0) return p;
-    if ((sched == SCHED_FLAT || sched == SCHED_FLAT_AG || sched == SCHED_FLAT_SEQ || sched == SCHED_FLAT_1SHOT) &&
-        n > 1) {
+    if (flat_family(sched) && n > 1) {
         Plan f = build_plan_flat(mode, n, me, k_in, b, g, slices, sched == SCHED_FLAT_AG, sched != SCHED_FLAT_SEQ,
                                  sched == SCHED_FLAT_1SHOT && mode == MODE_ALLREDUCE);
         if (!f.error) return f;
@@ -2020,20 +1978,13 @@ struct SymExec {
             for (const LocalOp& op : P[r].pre) local(r, op);
         const size_t ns = P[0].steps.size();
         for (size_t si = 0; si < ns; ++si) {
-            std::vector<std::vector<char>> used(n);
-            for (int r = 0; r < n; ++r) used[r].assign(P[r].steps[si].sends.size(), 0);
             std::vector<std::tuple<int, Ref, std::vector<int>>> land;
-            for (int r = 0; r < n; ++r)
-                for (const Xfer& rv : P[r].steps[si].recvs) {
-                    const auto& qs = P[rv.peer].steps[si].sends;
-                    size_t j = 0;
-                    while (j < qs.size() && (used[rv.peer][j] || qs[j].peer != r)) ++j;
-                    if (j == qs.size() || qs[j].count != rv.count) return false;
-                    used[rv.peer][j] = 1;
-                    std::vector<int> data(rv.count);
-                    for (uint64_t i = 0; i < rv.count; ++i) data[i] = *at(rv.peer, qs[j].ref, i);
-                    land.emplace_back(r, rv.ref, std::move(data));
-                }
+            const bool ok = match_step(P, si, [&](int r, const Xfer& rv, int q, const Xfer& sd) {
+                std::vector<int> data(rv.count);
+                for (uint64_t i = 0; i < rv.count; ++i) data[i] = *at(q, sd.ref, i);
+                land.emplace_back(r, rv.ref, std::move(data));
+            });
+            if (!ok) return false;
             for (auto& [r, ref, data] : land)
                 for (uint64_t i = 0; i < data.size(); ++i) *at(r, ref, i) = data[i];
             for (int r = 0; r < n; ++r)

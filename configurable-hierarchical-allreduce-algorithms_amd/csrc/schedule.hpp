@@ -43,8 +43,9 @@ enum LocalKind : uint8_t { L_COPY = 0, L_REDUCE = 1, L_COPY2D = 2, L_TREE = 3 };
 // L_COPY2D: rows x count elements, row r: dst + r*dpitch <- acc + r*spitch
 // L_TREE:   dst = one whole expression tree (chr_reduce_tree): leaves acc, ins[0], ins[1], ...
 //           in push order; comb[j] combines after leaf j; swaps[c] per combine
-constexpr int kTreeMaxLeaves = 8;  // kMaxLeaves, reduce_tree.hip
-constexpr int kTreeMaxDepth = 4;   // kTreeDepth
+// The host side's names for the tree kernel's limits (reduce_tree.hpp kMaxLeaves, kTreeDepth; tied in exec_local.cpp).
+constexpr int kTreeMaxLeaves = 8;
+constexpr int kTreeMaxDepth = 4;
 struct LocalOp {
     LocalKind kind;
     Ref dst;
@@ -164,6 +165,10 @@ enum Sched : int {
 };
 // A schedule a plan can be built for (every Sched value; not CHR_SCHEDULE_AUTO).
 inline bool plan_schedule(int s) { return (s >= SCHED_REFERENCE && s <= SCHED_FLAT_SEQ) || s == SCHED_FLAT_1SHOT; }
+// The schedules build_plan_flat compiles.
+inline bool flat_family(int s) {
+    return s == SCHED_FLAT || s == SCHED_FLAT_AG || s == SCHED_FLAT_SEQ || s == SCHED_FLAT_1SHOT;
+}
 // `commutative`: MPI_Op_commutative of the call's op (every predefined op is; a user op as created).  Only the MPICH
 // baselines that branch on it read it (build_plan_mpich); CHiArA's own schedules take the reference's operand
 // order for any op.

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "chiara.h"
+#include "schedule.hpp"  // kTreeMaxLeaves
 
 namespace chr {
 
@@ -40,16 +41,11 @@ bool lookup(int op, UserOp* out) {
     return true;
 }
 
-int hip_status(hipError_t e) {
-    if (e == hipSuccess) return CHR_SUCCESS;
-    return e == hipErrorOutOfMemory ? CHR_ERR_OUT_OF_MEMORY : CHR_ERR_HIP;
-}
-
 // The launcher's verdict: 0 = enqueued; anything else = the op refused the call (e.g. a type it does not implement).
 int call(const UserOp& u, void* out, const void* acc, const void* const* ins, int m, size_t n, int dtype, bool rf,
          hipStream_t s) {
     if (u.fn(out, acc, ins, m, n, (chr_dtype)dtype, rf ? 1 : 0, s, u.ctx) != 0) return CHR_ERR_UNSUPPORTED;
-    return hip_status(hipGetLastError());
+    return hip_code(hipGetLastError());
 }
 
 // One post-order program (launch_reduce_tree's contract): push leaf j, then comb[j] combines, each popping the top
@@ -62,7 +58,7 @@ int call(const UserOp& u, void* out, const void* acc, const void* const* ins, in
 int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, const uint8_t* comb,
               const uint8_t* swaps, size_t n, int dtype, hipStream_t s) {
     const size_t bytes = n * dtype_size(dtype);
-    void* slot[8] = {};  // stack positions: at most 8 leaves (tree_program_ok)
+    void* slot[kTreeMaxLeaves] = {};  // stack positions: one per leaf at most (tree_program_ok)
     struct Val {
         const void* p;
         bool leaf;
@@ -85,7 +81,7 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
         }
         if (!dst) {
             if (!slot[ch.pos])
-                if (int e = hip_status(hipMallocAsync(&slot[ch.pos], bytes, s))) return e;
+                if (int e = hip_code(hipMallocAsync(&slot[ch.pos], bytes, s))) return e;
             dst = slot[ch.pos];
         }
         const int e = call(u, dst, ch.acc, ch.ins.data(), (int)ch.ins.size(), n, dtype, ch.rf, s);
@@ -115,10 +111,10 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
     }
     if (!rc) rc = flush(true);
     if (!rc && st.size() == 1 && st[0].p != out)
-        rc = hip_status(hipMemcpyAsync(out, st[0].p, bytes, hipMemcpyDeviceToDevice, s));
+        rc = hip_code(hipMemcpyAsync(out, st[0].p, bytes, hipMemcpyDeviceToDevice, s));
     for (void* q : slot)
         if (q) {
-            const int e = hip_status(hipFreeAsync(q, s));
+            const int e = hip_code(hipFreeAsync(q, s));
             if (!rc) rc = e;
         }
     return rc;
@@ -145,13 +141,13 @@ int user_trees(const UserOp& u, const TreeJob* jobs, int njobs, int dtype, hipSt
                 ut.comb[j] = jb.comb[j];
                 nc += jb.comb[j];
             }
-            for (int c = 0; c < nc && c < 8; ++c) ut.swaps[c] = jb.swaps && jb.swaps[c] ? 1 : 0;
+            for (int c = 0; c < nc && c < kTreeMaxLeaves; ++c) ut.swaps[c] = jb.swaps && jb.swaps[c] ? 1 : 0;
             ts.push_back(ut);
         }
         if (!ts.empty()) {
             const int cap = coresident_depth() > 0 ? kCoresidentWgPerCu : 0;
             if (u.tree_fn(ts.data(), (int)ts.size(), (chr_dtype)dtype, cap, s, u.ctx) == 0) {
-                if (int rc = hip_status(hipGetLastError())) return rc;
+                if (int rc = hip_code(hipGetLastError())) return rc;
                 handed = true;
             }
         }
@@ -182,7 +178,7 @@ bool valid_any(int dtype, int op) {
 int reduce_any(void* out, const void* acc, const void* const* ins, int m, size_t n, int dtype, int op, hipStream_t s,
                bool running_first) {
     UserOp u;
-    if (!is_user_op(op)) return hip_status(launch_reduce(out, acc, ins, m, n, dtype, op, s, running_first));
+    if (!is_user_op(op)) return hip_code(launch_reduce(out, acc, ins, m, n, dtype, op, s, running_first));
     if (!lookup(op, &u)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
     return call(u, out, acc, ins, m, n, dtype, running_first, s);
@@ -191,10 +187,10 @@ int reduce_any(void* out, const void* acc, const void* const* ins, int m, size_t
 int reduce_tree_any(void* out, const void* const* leaves, int nl, const uint8_t* comb, const uint8_t* swaps, size_t n,
                     int dtype, int op, hipStream_t s) {
     UserOp u;
-    if (!is_user_op(op)) return hip_status(launch_reduce_tree(out, leaves, nl, comb, swaps, n, dtype, op, s));
+    if (!is_user_op(op)) return hip_code(launch_reduce_tree(out, leaves, nl, comb, swaps, n, dtype, op, s));
     if (!lookup(op, &u)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
-    if (nl < 1 || nl > 8) return CHR_ERR_INVALID_ARG;
+    if (nl < 1 || nl > kTreeMaxLeaves) return CHR_ERR_INVALID_ARG;
     TreeJob jb{};
     jb.out = out;
     for (int j = 0; j < nl; ++j) jb.leaves[j] = leaves[j];
@@ -207,7 +203,7 @@ int reduce_tree_any(void* out, const void* const* leaves, int nl, const uint8_t*
 
 int reduce_tree_multi_any(const TreeJob* jobs, int njobs, int dtype, int op, hipStream_t s) {
     UserOp u;
-    if (!is_user_op(op)) return hip_status(launch_reduce_tree_multi(jobs, njobs, dtype, op, s));
+    if (!is_user_op(op)) return hip_code(launch_reduce_tree_multi(jobs, njobs, dtype, op, s));
     if (!lookup(op, &u)) return CHR_ERR_INVALID_ARG;
     return user_trees(u, jobs, njobs, dtype, s);
 }

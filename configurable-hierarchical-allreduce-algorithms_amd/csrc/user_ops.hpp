@@ -6,10 +6,20 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 
 #include "chr_internal.hpp"
 
 namespace chr {
+
+// The library's one mapping of a HIP status to a chr_result; CHR_DEBUG prints what was lost in it.
+__attribute__((visibility("hidden"))) inline int hip_code(hipError_t e) {
+    if (e == hipSuccess) return CHR_SUCCESS;
+    if (e == hipErrorOutOfMemory) return CHR_ERR_OUT_OF_MEMORY;
+    if (std::getenv("CHR_DEBUG")) std::fprintf(stderr, "[chiara] HIP error: %s\n", hipGetErrorString(e));
+    return CHR_ERR_HIP;
+}
 
 // User ops take the chr_op codes [kUserOpBase, kUserOpBase + kMaxUserOps): above every predefined op and every
 // internal kernel code (kMaxSw ... kProdSw).

@@ -2,7 +2,7 @@
 plan for every mode, n <= 8, b, k in 2..9, several counts, pipeline depths and all six
 schedules -- messages pair up step by step with equal sizes, every buffer reference stays
 inside its declared buffer, and no plan writes the send buffer: no local op's destination, no
-receive and no allgather region is BUF_SEND, in `pre` or in any step (the executor aliases SEND
+receive and no allgather region is BUF_SEND, in `pre` or in any step (the executors alias SEND
 to RECV for CHR_IN_PLACE, so the rule holds for every plan; the device side is
 tests/test_gpu_footprint.py) (tools/plan_fuzz.cpp; the full n <= 16 grid, 88 064 plans, was run
 the same way before the send-buffer rule)."""

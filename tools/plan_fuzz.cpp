@@ -1,10 +1,10 @@
 // plan_fuzz.cpp -- host-only sweep of the schedule compiler under AddressSanitizer / UBSan.
 // Builds every rank's plan for every (mode, n, k, b, count, slices, schedule) in a wide grid,
 // checks the plans pair up (every send has a matching receive in the same step with the same
-// size), that every buffer reference stays inside its declared buffer and that no plan ever writes
-// the send buffer (no local op's dst, no receive, no allgather region is BUF_SEND, in `pre` or in
+// size; by this tool's own map and by the executors' match_step, plan_util.hpp), that every
+// buffer reference stays inside its declared buffer and that no plan ever writes the send buffer (no local op's dst, no receive, no allgather region is BUF_SEND, in `pre` or in
 // any step: the collectives take `const void* sendbuf`; plans do not know about CHR_IN_PLACE, the
-// executor aliases SEND to RECV, so the rule holds for every plan), and describes each plan
+// executors alias SEND to RECV, so the rule holds for every plan), and describes each plan
 // (exercising the printer).  Run by tests/test_plan_fuzz.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -Iinclude -I<pkg>/csrc tools/plan_fuzz.cpp <pkg>/csrc/schedule.cpp -o /tmp/plan_fuzz
@@ -14,7 +14,7 @@
 #include <tuple>
 #include <vector>
 
-#include "schedule.hpp"
+#include "plan_util.hpp"
 
 using namespace chr;
 
@@ -110,6 +110,12 @@ int main(int argc, char** argv) {
                                         }
                                     }
                                     if (snd != rcv) fail("unmatched messages", mode, n, k, b, count, sched);
+                                    // the executors' own matcher (plan_util.hpp) agrees: one pair per receive
+                                    size_t nrecv = 0, npairs = 0;
+                                    for (const Plan& p : P) nrecv += p.steps[s].recvs.size();
+                                    if (!match_step(P, s, [&](int, const Xfer&, int, const Xfer&) { ++npairs; }) ||
+                                        npairs != nrecv)
+                                        fail("match_step", mode, n, k, b, count, sched);
                                 }
                                 for (const Plan& p : P)
                                     for (const LocalOp& op : p.pre) {
