@@ -137,6 +137,37 @@ def op_create(launcher, commute=False, ctx=None, tree=None):
     return op.value
 
 
+def type_contiguous(count, base):
+    """A derived element type (chr_type_contiguous, MPI_Type_contiguous + MPI_Type_commit): one element is `count`
+    consecutive `base` elements.  Returns the type code (64..127), valid with a user-defined op in every reduction and
+    collective and with no op in the data-movement collectives; counts are then in derived elements."""
+    t = ctypes.c_int(0)
+    check(lib().chr_type_contiguous(int(count), int(base), ctypes.byref(t)), "chr_type_contiguous")
+    return t.value
+
+
+def type_free(t):
+    """Release a derived type (chr_type_free); its code may be handed out again."""
+    return lib().chr_type_free(int(t))
+
+
+def type_size(t):
+    """Bytes of one element (chr_type_size, MPI_Type_size): predefined and derived types.  Byte math on a type code
+    goes through this; DTYPE_SIZE lists the predefined types only."""
+    if t in DTYPE_SIZE:
+        return DTYPE_SIZE[t]
+    n = ctypes.c_size_t(0)
+    check(lib().chr_type_size(int(t), ctypes.byref(n)), "chr_type_size")
+    return n.value
+
+
+def type_get_contiguous(t):
+    """(base, count) of a derived type (chr_type_get_contiguous); a predefined type returns (itself, 1)."""
+    base, count = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().chr_type_get_contiguous(int(t), ctypes.byref(base), ctypes.byref(count)), "chr_type_get_contiguous")
+    return base.value, count.value
+
+
 def op_free(op):
     """Release a user-defined op (chr_op_free); its code may be handed out again."""
     rc = lib().chr_op_free(op)

@@ -38,7 +38,7 @@ const char* chr_error_string(int code) {
 }
 
 int chr_reduce_local(const void* in, void* inout, size_t n, chr_dtype dtype, chr_op op, hipStream_t stream) {
-    if (!chr::valid_any(dtype, op)) return CHR_ERR_INVALID_ARG;
+    if (int rc = chr::check_any(dtype, op)) return rc;
     if (n == 0) return CHR_SUCCESS;
     if (!in || !inout) return CHR_ERR_INVALID_ARG;
     const void* ins[1] = {in};
@@ -52,7 +52,8 @@ int chr_reduce_multi(void* out, const void* acc, const void* const* ins, int m, 
 
 int chr_reduce_multi_ex(void* out, const void* acc, const void* const* ins, int m, size_t n, chr_dtype dtype,
                         chr_op op, int flags, hipStream_t stream) {
-    if (!chr::valid_any(dtype, op) || m < 0 || (flags & ~CHR_REDUCE_RUNNING_FIRST)) return CHR_ERR_INVALID_ARG;
+    if (int rc = chr::check_any(dtype, op)) return rc;
+    if (m < 0 || (flags & ~CHR_REDUCE_RUNNING_FIRST)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
     if (!out || !acc || (m > 0 && !ins)) return CHR_ERR_INVALID_ARG;
     for (int j = 0; j < m; ++j)
@@ -62,7 +63,8 @@ int chr_reduce_multi_ex(void* out, const void* acc, const void* const* ins, int 
 
 int chr_reduce_tree(void* out, const void* const* leaves, int nleaves, const unsigned char* comb,
                     const unsigned char* swaps, size_t n, chr_dtype dtype, chr_op op, hipStream_t stream) {
-    if (!chr::valid_any(dtype, op) || nleaves < 1 || !comb || !leaves) return CHR_ERR_INVALID_ARG;
+    if (int rc = chr::check_any(dtype, op)) return rc;
+    if (nleaves < 1 || !comb || !leaves) return CHR_ERR_INVALID_ARG;
     uint32_t cb = 0, sb = 0;
     if (!chr::tree_program_ok(nleaves, comb, swaps, &cb, &sb)) return CHR_ERR_UNSUPPORTED;
     if (n == 0) return CHR_SUCCESS;
@@ -75,8 +77,8 @@ int chr_reduce_tree(void* out, const void* const* leaves, int nleaves, const uns
 int chr_reduce_tree_batch(void* const* outs, const void* const* leaves, int ntrees, int nleaves,
                           const unsigned char* comb, const unsigned char* swaps, size_t n, chr_dtype dtype, chr_op op,
                           hipStream_t stream) {
-    if (!chr::valid_any(dtype, op) || ntrees < 0 || nleaves < 1 || nleaves > chr::kTreeMaxLeaves)
-        return CHR_ERR_INVALID_ARG;
+    if (int rc = chr::check_any(dtype, op)) return rc;
+    if (ntrees < 0 || nleaves < 1 || nleaves > chr::kTreeMaxLeaves) return CHR_ERR_INVALID_ARG;
     if (ntrees > 0 && (!outs || !leaves || !comb)) return CHR_ERR_INVALID_ARG;
     std::vector<chr::TreeJob> jobs((size_t)ntrees);
     for (int t = 0; t < ntrees; ++t) {
@@ -101,6 +103,7 @@ int chr_reduce_tree_batch(void* const* outs, const void* const* leaves, int ntre
 
 int chr_fill(void* buf, size_t n, chr_dtype dtype, int pattern, uint64_t seed, int rank, uint64_t count_for_seq,
              hipStream_t stream) {
+    // the patterns are defined on the predefined types only: a derived type has no size here
     if (!chr::dtype_size(dtype) || (pattern < 0 || pattern > 3)) return CHR_ERR_INVALID_ARG;
     if (n == 0) return CHR_SUCCESS;
     if (!buf) return CHR_ERR_INVALID_ARG;

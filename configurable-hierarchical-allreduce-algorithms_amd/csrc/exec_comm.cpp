@@ -28,7 +28,7 @@ static int rccl_group(Post&& post) {
 }
 
 static int enqueue_plan(chr_comm* c, const Plan& p, const void* send, void* recv, int dtype, int op, bool* posted) {
-    const size_t es = chr::dtype_size(dtype);
+    const size_t es = chr::elem_size(dtype);
     hipError_t e = c->reserve_scratch(p.acc_elems * es, p.stage_elems * es);
     if (e != hipSuccess) return hip_code(e);
     Bufs B{(const char*)send, (char*)recv, (char*)c->acc.p, (char*)c->stage.p, es};
@@ -124,7 +124,7 @@ int enqueue_rccl(chr_comm* c, const Plan& p, const void* send, void* recv, int d
 // is what bounds small messages.  Scratch is sized before capture (no allocation inside it); if
 // that grows a buffer, every cached graph is dropped (they point into the old one).
 static int launch_graph(chr_comm* c, const Plan& p, const void* send, void* recv, int dtype, int op) {
-    const size_t es = chr::dtype_size(dtype);
+    const size_t es = chr::elem_size(dtype);
     hipError_t e = c->reserve_scratch(p.acc_elems * es, p.stage_elems * es);
     if (e != hipSuccess) return hip_code(e);
     auto key = std::make_tuple(&p, send, recv, dtype, op, c->overlap);
@@ -232,11 +232,11 @@ int agree_min(chr_comm* c, int mine, int* all) {
 
 int run_collective(chr_comm* c, int sched, int slices, int mode, const void* send, void* recv, size_t count, int dtype,
                    int op, int k, int b, bool sync) {
-    const Plan& p = c->plan(mode, k, b, count, chr::dtype_size(dtype), sched, slices, chr::op_commutative(op));
+    const Plan& p = c->plan(mode, k, b, count, chr::elem_size(dtype), sched, slices, chr::op_commutative(op));
     if (p.error) return p.error;
     if (p.g.total == 0) return CHR_SUCCESS;
     if (!recv && p.recv_elems) return CHR_ERR_INVALID_ARG;  // a rank whose plan writes no output may pass NULL
-    const size_t es = chr::dtype_size(dtype);
+    const size_t es = chr::elem_size(dtype);
     const void* input = nullptr;
     if (int rc = resolve_input(mode, send, recv, c->rank, count, es, &input)) return rc;
     if (!input && p.send_elems) return CHR_ERR_INVALID_ARG;  // a rank whose plan reads no input may pass NULL
@@ -296,7 +296,8 @@ int run_collective(chr_comm* c, int sched, int slices, int mode, const void* sen
 int collective(chr_comm* c, int mode, const void* send, void* recv, size_t count, int dtype, int op, int k, int b,
                bool sync) {
     // allgather moves elements of any type (its op is unused)
-    if (!c || !valid_args(mode, dtype, op)) return CHR_ERR_INVALID_ARG;
+    if (!c) return CHR_ERR_INVALID_ARG;
+    if (int rc = check_args(mode, dtype, op)) return rc;
     if (c->failed) return CHR_ERR_ABORTED;
     int sched = c->sched, slices = c->slices;
     if (sched == CHR_SCHEDULE_AUTO) {

@@ -41,7 +41,7 @@ size_t host_window_elems(const chr_comm* c, int mode, size_t count, size_t es) {
 // not split (one window would cover it).
 int run_host_windows(chr_comm* c, int sched, int slices, int mode, const void* input, void* recv, size_t count,
                      int dtype, int op, int k, int b) {
-    const size_t es = chr::dtype_size(dtype), n = (size_t)c->nranks;
+    const size_t es = chr::elem_size(dtype), n = (size_t)c->nranks;
     const size_t w = host_window_elems(c, mode, count, es);
     if (w == 0) return -1;
     const size_t block = mode == chr::MODE_ALLREDUCE ? count / n : count;  // recvcount

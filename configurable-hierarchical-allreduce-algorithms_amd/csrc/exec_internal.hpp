@@ -169,7 +169,7 @@ int pick_slices(int setting, uint64_t count, int mode, int nranks, int b, size_t
 
 // exec_local.cpp: local ops of one rank on one stream
 bool is_device_ptr(const void* p);
-bool valid_args(int mode, int dtype, int op);
+int check_args(int mode, int dtype, int op);
 // Where rank `rank` reads its input: `send`, or under CHR_IN_PLACE its place in `recv` (CHR_ERR_INVALID_ARG for the
 // modes that have no in-place form).
 int resolve_input(int mode, const void* send, void* recv, int rank, size_t count, size_t es, const void** input);

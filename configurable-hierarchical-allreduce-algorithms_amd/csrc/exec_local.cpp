@@ -1,6 +1,6 @@
 // exec_local.cpp -- one rank's local ops on one stream: the fold / tree / copy runner, the batching of a step's trees
 // into shared launches (which trees share one is plan_util.hpp's batched_runs), and the argument checks both
-// executors make (valid_args, resolve_input, is_device_ptr).
+// executors make (check_args, resolve_input, is_device_ptr).
 #include "exec_internal.hpp"
 #include "reduce_tree.hpp"  // only for the limits below
 
@@ -101,10 +101,11 @@ bool is_device_ptr(const void* p) {
 }
 
 // The (dtype, op) pairs a mode accepts: the data-movement collectives (allgather, the stand-alone
-// intra scatter) move elements of any type and ignore op.
-bool valid_args(int mode, int dtype, int op) {
-    if (mode == MODE_ALLGATHER || mode == MODE_INTRA_SCATTER) return dtype_size(dtype) != 0;
-    return valid_any(dtype, op);
+// intra scatter) move elements of any type, derived ones included, and ignore op.  A chr_result (check_any).
+int check_args(int mode, int dtype, int op) {
+    if (mode == MODE_ALLGATHER || mode == MODE_INTRA_SCATTER)
+        return elem_size(dtype) != 0 ? CHR_SUCCESS : CHR_ERR_INVALID_ARG;
+    return check_any(dtype, op);
 }
 
 int resolve_input(int mode, const void* send, void* recv, int rank, size_t count, size_t es, const void** input) {

@@ -8,12 +8,13 @@ namespace chr {
 
 int local_collective(chr_local_group* g, int mode, const void* const* sends, void* const* recvs, size_t count,
                      int dtype, int op, int k, int b) {
-    if (!g || !sends || !recvs || !valid_args(mode, dtype, op)) return CHR_ERR_INVALID_ARG;
+    if (!g || !sends || !recvs) return CHR_ERR_INVALID_ARG;
+    if (int rc = check_args(mode, dtype, op)) return rc;
     const int n = g->nranks;
     // the MPICH baselines branch on MPI_Op_commutative (build_plan_mpich); CHiArA's own collectives take any op
     const bool commutative = chr::op_commutative(op);
-    const int depth = pick_slices(g->slices, count, mode, n, b, chr::dtype_size(dtype), g->sched);
-    auto key = std::make_tuple(mode, k, b, (uint64_t)count, (int)chr::dtype_size(dtype), depth, g->sched, commutative);
+    const int depth = pick_slices(g->slices, count, mode, n, b, chr::elem_size(dtype), g->sched);
+    auto key = std::make_tuple(mode, k, b, (uint64_t)count, (int)chr::elem_size(dtype), depth, g->sched, commutative);
     auto it = g->plans.find(key);
     if (it == g->plans.end()) {
         std::vector<Plan> v;
@@ -24,7 +25,7 @@ int local_collective(chr_local_group* g, int mode, const void* const* sends, voi
     const std::vector<Plan>& P = it->second;
     if (P[0].error) return P[0].error;
     if (P[0].g.total == 0) return CHR_SUCCESS;
-    const size_t es = chr::dtype_size(dtype);
+    const size_t es = chr::elem_size(dtype);
     hipError_t e = hipSetDevice(g->device);
     if (e != hipSuccess) return hip_code(e);
     std::vector<Bufs> B(n);

@@ -95,7 +95,7 @@ int tune_schedule(chr_comm* c, int mode, const void* send, void* recv, size_t co
     *slices_out = c->slices;
     if (chr::is_unpipelined(mode) || c->nranks < 2) return CHR_SUCCESS;
     if (c->failed) return CHR_ERR_ABORTED;
-    const size_t es = chr::dtype_size(dtype);
+    const size_t es = chr::elem_size(dtype);
     auto key = std::make_tuple(mode, (uint64_t)count, (int)es, k, b, c->slices, c->overlap);
     auto it = c->tuned.find(key);
     if (it != c->tuned.end()) {
@@ -196,12 +196,12 @@ int tune_schedule(chr_comm* c, int mode, const void* send, void* recv, size_t co
 
 extern "C" int chr_comm_tuned_schedule(const chr_comm* c, int mode, size_t count, chr_dtype dtype, int k, int b,
                                        int* schedule, int* slices) {
-    if (!c || !schedule || !slices || !chr::dtype_size(dtype)) return CHR_ERR_INVALID_ARG;
+    if (!c || !schedule || !slices || !chr::elem_size(dtype)) return CHR_ERR_INVALID_ARG;
     if (mode != chr::MODE_ALLREDUCE && mode != chr::MODE_REDUCE_SCATTER) return CHR_ERR_INVALID_ARG;
     if (c->failed) return CHR_ERR_ABORTED;
     if (c->sched != CHR_SCHEDULE_AUTO) {  // a fixed schedule: it, at the depth such a call runs
         const int P =
-            chr::pick_slices(c->slices, (uint64_t)count, mode, c->nranks, b, chr::dtype_size(dtype), c->sched);
+            chr::pick_slices(c->slices, (uint64_t)count, mode, c->nranks, b, chr::elem_size(dtype), c->sched);
         // the arguments a call would reject (k < 2, nranks % b, count % nranks) are rejected here too
         const chr::Plan p = chr::build_plan((chr::Mode)mode, c->nranks, c->rank, k, b, (uint64_t)count, P, c->sched);
         if (p.error) return p.error;
@@ -209,7 +209,7 @@ extern "C" int chr_comm_tuned_schedule(const chr_comm* c, int mode, size_t count
         *slices = P;
         return CHR_SUCCESS;
     }
-    auto it = c->tuned.find(std::make_tuple(mode, (uint64_t)count, (int)chr::dtype_size(dtype), k, b, c->slices,
+    auto it = c->tuned.find(std::make_tuple(mode, (uint64_t)count, (int)chr::elem_size(dtype), k, b, c->slices,
                                             c->overlap));
     if (it == c->tuned.end()) return CHR_ERR_INVALID_ARG;
     *schedule = it->second.first;

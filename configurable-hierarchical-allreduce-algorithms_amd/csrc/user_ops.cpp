@@ -32,6 +32,13 @@ struct UserOp {
 std::mutex g_mu;
 UserOp g_ops[kMaxUserOps];
 
+// Derived types: base and count of each live code; the same lock as the ops.
+struct UserType {
+    int base = 0, count = 0;
+    bool live = false;
+};
+UserType g_types[kMaxUserTypes];
+
 bool lookup(int op, UserOp* out) {
     if (!is_user_op(op)) return false;
     std::lock_guard<std::mutex> lk(g_mu);
@@ -57,7 +64,10 @@ int call(const UserOp& u, void* out, const void* acc, const void* const* ins, in
 // value, never as an input), the last one straight to `out` unless `out` is one of its inputs.
 int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, const uint8_t* comb,
               const uint8_t* swaps, size_t n, int dtype, hipStream_t s) {
-    const size_t bytes = n * dtype_size(dtype);
+    const size_t bytes = n * elem_size(dtype);
+    // A derived type's chunks start at multiples of its size, often off 16-byte alignment; the header's kernels stream
+    // operands that are congruent modulo 16, so a slot starts at the residue of `out`.
+    const size_t skew = is_derived_type(dtype) ? (uintptr_t)out & 15 : 0;
     void* slot[kTreeMaxLeaves] = {};  // stack positions: one per leaf at most (tree_program_ok)
     struct Val {
         const void* p;
@@ -81,8 +91,8 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
         }
         if (!dst) {
             if (!slot[ch.pos])
-                if (int e = hip_code(hipMallocAsync(&slot[ch.pos], bytes, s))) return e;
-            dst = slot[ch.pos];
+                if (int e = hip_code(hipMallocAsync(&slot[ch.pos], bytes + skew, s))) return e;
+            dst = static_cast<char*>(slot[ch.pos]) + skew;
         }
         const int e = call(u, dst, ch.acc, ch.ins.data(), (int)ch.ins.size(), n, dtype, ch.rf, s);
         st[ch.pos] = {dst, false};
@@ -169,11 +179,25 @@ bool op_commutative(int op) {
     return !is_user_op(op) || (lookup(op, &u) && u.commute);
 }
 
-bool valid_any(int dtype, int op) {
-    if (!is_user_op(op)) return valid_dtype_op(dtype, op);
-    UserOp u;
-    return dtype_size(dtype) != 0 && lookup(op, &u);
+bool is_derived_type(int dtype) { return dtype >= kUserTypeBase && dtype < kUserTypeBase + kMaxUserTypes; }
+
+size_t elem_size(int dtype) {
+    if (!is_derived_type(dtype)) return dtype_size(dtype);
+    std::lock_guard<std::mutex> lk(g_mu);
+    const UserType& t = g_types[dtype - kUserTypeBase];
+    return t.live ? (size_t)t.count * dtype_size(t.base) : 0;
 }
+
+int check_any(int dtype, int op) {
+    if (!is_user_op(op)) {
+        if (is_derived_type(dtype) && elem_size(dtype) != 0 && op >= 0 && op < kNumOps) return CHR_ERR_UNSUPPORTED;
+        return valid_dtype_op(dtype, op) ? CHR_SUCCESS : CHR_ERR_INVALID_ARG;
+    }
+    UserOp u;
+    return elem_size(dtype) != 0 && lookup(op, &u) ? CHR_SUCCESS : CHR_ERR_INVALID_ARG;
+}
+
+bool valid_any(int dtype, int op) { return check_any(dtype, op) == CHR_SUCCESS; }
 
 int reduce_any(void* out, const void* acc, const void* const* ins, int m, size_t n, int dtype, int op, hipStream_t s,
                bool running_first) {
@@ -239,6 +263,54 @@ int chr_op_free(chr_op op) {
     chr::UserOp& u = chr::g_ops[(int)op - chr::kUserOpBase];
     if (!u.live) return CHR_ERR_INVALID_ARG;
     u = chr::UserOp{};
+    return CHR_SUCCESS;
+}
+
+int chr_type_contiguous(int count, chr_dtype base, chr_dtype* newtype) {
+    const size_t bs = chr::dtype_size((int)base);  // 0 for a derived base: no nesting
+    if (!newtype || count < 1 || !bs || (size_t)count > chr::kMaxElemBytes / bs) return CHR_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(chr::g_mu);
+    for (int i = 0; i < chr::kMaxUserTypes; ++i) {
+        chr::UserType& t = chr::g_types[i];
+        if (t.live) continue;
+        t.base = (int)base;
+        t.count = count;
+        t.live = true;
+        *newtype = (chr_dtype)(chr::kUserTypeBase + i);
+        return CHR_SUCCESS;
+    }
+    return CHR_ERR_UNSUPPORTED;  // every code taken
+}
+
+int chr_type_free(chr_dtype type) {
+    if (!chr::is_derived_type((int)type)) return CHR_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(chr::g_mu);
+    chr::UserType& t = chr::g_types[(int)type - chr::kUserTypeBase];
+    if (!t.live) return CHR_ERR_INVALID_ARG;
+    t = chr::UserType{};
+    return CHR_SUCCESS;
+}
+
+int chr_type_size(chr_dtype type, size_t* bytes) {
+    const size_t es = chr::elem_size((int)type);
+    if (!bytes || !es) return CHR_ERR_INVALID_ARG;
+    *bytes = es;
+    return CHR_SUCCESS;
+}
+
+int chr_type_get_contiguous(chr_dtype type, chr_dtype* base, int* count) {
+    if (!base || !count) return CHR_ERR_INVALID_ARG;
+    if (!chr::is_derived_type((int)type)) {
+        if (!chr::dtype_size((int)type)) return CHR_ERR_INVALID_ARG;
+        *base = type;
+        *count = 1;
+        return CHR_SUCCESS;
+    }
+    std::lock_guard<std::mutex> lk(chr::g_mu);
+    const chr::UserType& t = chr::g_types[(int)type - chr::kUserTypeBase];
+    if (!t.live) return CHR_ERR_INVALID_ARG;
+    *base = (chr_dtype)t.base;
+    *count = t.count;
     return CHR_SUCCESS;
 }
 

@@ -26,10 +26,23 @@ __attribute__((visibility("hidden"))) inline int hip_code(hipError_t e) {
 constexpr int kUserOpBase = 64;
 constexpr int kMaxUserOps = 64;
 
+// Derived element types (chr_type_contiguous) take the chr_dtype codes [kUserTypeBase, kUserTypeBase + kMaxUserTypes),
+// above every predefined type.  One element is `count` consecutive base elements, kMaxElemBytes at most.
+constexpr int kUserTypeBase = 64;
+constexpr int kMaxUserTypes = 64;
+constexpr size_t kMaxElemBytes = 65536;
+
 bool is_user_op(int op);
+bool is_derived_type(int dtype);
+// MPI_Type_size: dtype_size for a predefined code, the registry for a live derived one, 0 for anything else.  Every
+// host-side byte count goes through this; dtype_size stays the kernels' constexpr table of the predefined types.
+size_t elem_size(int dtype);
 // MPI_Op_commutative: every predefined op is commutative; a user op as chr_op_create recorded it.
 bool op_commutative(int op);
-// A live user op on a type with a size, or a (type, op) pair MPICH's table accepts (valid_dtype_op).
+// CHR_SUCCESS for a live user op on a type with a size (derived types included) and for a (type, op) pair MPICH's
+// table accepts (valid_dtype_op); CHR_ERR_UNSUPPORTED for a predefined op on a live derived type (MPI's predefined
+// ops take no derived type: MPICH answers MPI_ERR_OP); CHR_ERR_INVALID_ARG otherwise.  valid_any: the first of these.
+int check_any(int dtype, int op);
 bool valid_any(int dtype, int op);
 
 // The reductions: chr_result codes.  reduce_any is MPI_Reduce_local chained over ins (launch_reduce's contract);

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CHR_ABI_VERSION 11 /* 11: user-defined ops (chr_op_create; added since, no signature changed: chr_op_create_tree, CHR_OP_USER_LAST); 10: chr_comm_get_overlap; 9: chr_comm_info; 8: the stand-alone phase collectives (chr_intra_reduce_scatter_radix_batch, ...) */
+#define CHR_ABI_VERSION 11 /* 11: user-defined ops (chr_op_create; added since, no signature changed: chr_op_create_tree, CHR_OP_USER_LAST, chr_type_contiguous / chr_type_free / chr_type_size / chr_type_get_contiguous, CHR_DTYPE_USER_LAST); 10: chr_comm_get_overlap; 9: chr_comm_info; 8: the stand-alone phase collectives (chr_intra_reduce_scatter_radix_batch, ...) */
 
 /* Element types.  The reference is generic over MPI_Datatype (all_reduce_radix_batch.cpp:202-204,
  * sizes from MPI_Type_size at :234-277); these are the MPI predefined types MPICH's
@@ -49,8 +49,35 @@ typedef enum {
     CHR_SHORT_INT = 15,   /* MPI_SHORT_INT   {short; int}    8 B (MPI_Type_size 6) */
     /* C99 complex types: SUM and PROD (C99 Annex G multiplication, as MPICH's C loop does) */
     CHR_C_FLOAT_COMPLEX = 16,   /* MPI_C_FLOAT_COMPLEX (MPI_C_COMPLEX)  8 B */
-    CHR_C_DOUBLE_COMPLEX = 17   /* MPI_C_DOUBLE_COMPLEX                16 B */
+    CHR_C_DOUBLE_COMPLEX = 17,  /* MPI_C_DOUBLE_COMPLEX                16 B */
+    CHR_DTYPE_USER_LAST = 127   /* the last derived-type code: chr_type_contiguous's 64..127 lie inside the enum's range */
 } chr_dtype;
+
+/* ---- derived element types: MPI_Type_contiguous's analogue ----------------------------
+ * The reference is generic over MPI_Datatype: it takes MPI_Type_size and moves bytes, so a contiguous type with a
+ * user-defined op runs through every one of its collectives.  chr_type_contiguous is MPI_Type_contiguous +
+ * MPI_Type_commit: one element of `newtype` is `count` consecutive `base` elements (a Welford record, a double-double,
+ * an {x, y, z} triple).  `base` is a predefined type (no nesting), count >= 1, and an element is at most 65536 bytes
+ * (CHR_ERR_INVALID_ARG otherwise).  Codes 64..127; 64 types may be live at once (CHR_ERR_UNSUPPORTED when all are
+ * taken); the registry is thread-safe and needs no device.
+ *
+ * A derived type is valid with a live user op (chr_op_create) in chr_reduce_local, chr_reduce_multi(_ex),
+ * chr_reduce_tree(_batch), CHiArA's collectives and stand-alone phases, and the MPICH baselines, on communicators and
+ * local groups, device and host buffers; and with no op in the data-movement collectives (allgather, intra scatter).
+ * Every count (count, recvcount, sendcount, n) is in derived elements, the preconditions (count % nranks, ...) apply
+ * to that count, and the op's launchers receive the derived code as their chr_dtype argument and n in derived
+ * elements: no message, slice, fold or tree ever begins or ends inside an element.  A predefined op on a derived type
+ * is CHR_ERR_UNSUPPORTED before anything is enqueued (MPI's predefined ops take no derived type: MPICH answers
+ * MPI_ERR_OP), chr_fill on one CHR_ERR_INVALID_ARG.
+ *
+ * chr_type_free releases the code (CHR_ERR_INVALID_ARG for a predefined, dead or unknown one).  Freeing a type that
+ * cached plans or tuning entries were built for is harmless: their keys hold the element size, not the code.
+ * chr_type_size is MPI_Type_size for predefined and derived types; chr_type_get_contiguous returns a derived type's
+ * base and count (MPI_Type_get_contents' information), a predefined type itself and 1. */
+int chr_type_contiguous(int count, chr_dtype base, chr_dtype* newtype);
+int chr_type_free(chr_dtype type);
+int chr_type_size(chr_dtype type, size_t* bytes);
+int chr_type_get_contiguous(chr_dtype type, chr_dtype* base, int* count);
 
 /* Reduction ops: MPI's predefined ops with MPICH 3.3.2's element semantics
  * (inout[i] = inout[i] OP in[i]), and MPICH's table of which (type, op) pairs it accepts.  SUM/PROD/

@@ -13,6 +13,15 @@
  * --ab NAME=LIB.so adds the one-pass rows of another build of tests/userop/halfadd_tree_op.hip (make -C tests/userop -f tree_op.mk ab:
    its flags plus e.g. -DCHR_USER_TREE_NT=0 -DCHR_USER_TREE_XCD_RUN_KIB=0): the A/B of the kernel's policy knobs.
 
+ * --struct: derived element types (chr_type_contiguous) of 12, 24, 32 and 48 bytes with tests/userop/struct_op.hip's
+   RotMix beside the f32 op at the same bytes -- folds m = 1 and 3 at 64 MiB per operand, trees of 2 and 4 leaves at
+   16 and 64 MiB per leaf (fraction of 8 TB/s at leaves + 1 units), the C4-shaped allreduce with f64 x 3 HalfAdd, and
+   the 8-leaf f64 x 3 tree at 16 MiB per leaf, which the register rule keeps from the vector kernel -- each row once
+   per build of struct_op.hip: the shipped one (groups at the sizes the header lists, every tree in one pass), grp0
+   (CHR_USER_GROUP_VEC=0: element-wise, the behaviour before the groups) and all (groups at every size that has them,
+   and the trees the register rule keeps from the vector kernel declined to the folds); make -C tests/userop -f
+   struct_op.mk all ab.  Only these rows run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -129,8 +138,80 @@ def tree_rows(rounds, variants, tree_fn, stream):
     return rows
 
 
+STRUCT_SHAPES = {"f32x3": (torch.float32, 3, ca.FLOAT32), "f64x3": (torch.float64, 3, ca.FLOAT64),
+                 "f64x4": (torch.float64, 4, ca.FLOAT64), "f64x6": (torch.float64, 6, ca.FLOAT64)}
+STRUCT_BUILDS = {"shipped": "libstruct_op.so", "grp0": "libstruct_op_grp0.so", "all": "libstruct_op_all.so"}
+TREE_PROGS = {2: ([0, 1], [0]), 4: ([0, 1, 1, 1], [0, 0, 0]), 8: (C4_COMB, C4_SWAPS)}
+
+
+def struct_rows(rounds, stream):
+    """Rows of --struct, per round; every variant of a row is timed back to back within the round."""
+    dev = torch.device("cuda:0")
+    libs = {b: ctypes.CDLL(os.path.join(REPO, "tests", "userop", so)) for b, so in STRUCT_BUILDS.items()}
+    tlib = ctypes.CDLL(os.path.join(REPO, "tests", "userop", "libhalfadd_tree_op.so"))
+
+    def addr(lib, name):
+        return ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
+
+    # (row label, element bytes, torch type, words per element, chr_dtype, {variant: op})
+    shapes = [("f32", 4, torch.float32, 1, ca.FLOAT32,
+               {"f32": ca.op_create(addr(tlib, "chr_test_halfadd"), tree=addr(tlib, "chr_test_halfadd_tree"))})]
+    for shape, (tdt, k, base) in STRUCT_SHAPES.items():
+        ops = {b: ca.op_create(addr(lib, f"chr_struct_RotMixK_{shape}"), tree=addr(lib, f"chr_struct_RotMixK_{shape}_tree"))
+               for b, lib in libs.items()}
+        shapes.append((shape, k * torch.empty(0, dtype=tdt).element_size(), tdt, k, ca.type_contiguous(k, base), ops))
+    rows = [{} for _ in range(rounds)]
+    for label, es, tdt, k, dt, ops in shapes:
+        for what, units, mib, reps in ([("fold", m + 1, 64, 60) for m in (1, 3)] +
+                                       [("tree", nl + 1, mib, 120 if mib == 16 else 60) for nl in (2, 4) for mib in (16, 64)] +
+                                       ([("tree", 9, 16, 120)] if label == "f64x3" else [])):
+            n = (mib << 20) // es
+            sets = max(1, (2 << 30) // (units * n * es))
+            bufs = [[torch.rand(n * k, device=dev, dtype=tdt) for _ in range(units)] for _ in range(sets)]
+            for r in range(rounds):
+                for variant, op in ops.items():
+                    if what == "fold":  # acc in place, m inputs: m + 2 units of traffic
+                        def go(i, op=op):
+                            s = bufs[i % sets]
+                            ca.check(ca.reduce_multi(s[0], s[0], s[1:], n, dt, op, stream))
+                        ms = timed(go, reps)
+                        rows[r][f"fold_m{units - 1}_64MiB_{label}_{variant}_GBps"] = round((units + 1) * n * es / ms / 1e6, 1)
+                    else:
+                        comb, swaps = TREE_PROGS[units - 1]
+
+                        def go(i, op=op):
+                            s = bufs[i % sets]
+                            ca.check(ca.reduce_tree(s[-1], s[:-1], comb, swaps, n, dt, op, stream))
+                        ms = timed(go, reps)
+                        rows[r][f"tree{units - 1}_{mib}MiB_{label}_{variant}_frac"] = round(units * n * es / (ms * 1e-3) / HBM_PEAK, 4)
+            del bufs
+    # the C4-shaped allreduce, 128 MiB per rank, f64 x 3 HalfAdd against the f32 op
+    nr, nbytes = 8, 128 << 20
+    g = ca.LocalGroup(nr, 0)
+    sends = [torch.rand(nbytes // 8, device=dev, dtype=torch.float64) for _ in range(nr)]
+    recvs = [torch.empty(nbytes // 8, device=dev, dtype=torch.float64) for _ in range(nr)]
+    dt24 = ca.type_contiguous(3, ca.FLOAT64)
+    c4 = [("f32", ca.FLOAT32, nbytes // 4, shapes[0][5]["f32"])]
+    for b, lib in libs.items():
+        c4.append((f"f64x3_{b}", dt24, nbytes // 24 // nr * nr,
+                   ca.op_create(addr(lib, "chr_struct_HalfAddK_f64x3"), tree=addr(lib, "chr_struct_HalfAddK_f64x3_tree"))))
+    for r in range(rounds):
+        for name, dt, cnt, op in c4:
+            for _ in range(2):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, dt, op, 4, 4))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, dt, op, 4, 4))
+            torch.cuda.synchronize()
+            rows[r][f"localgroup8_k4b4_128MiB_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+    g.destroy()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--no-folds", action="store_true", help="skip the fold rows")
     ap.add_argument("--ab", action="append", default=[], metavar="NAME=LIB.so",
@@ -141,6 +222,16 @@ def main():
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     out = {"tool": "tools/userop_bench.py", "tree_lib": "libhalfadd_tree_op.so"}
+    if a.struct:
+        out["builds"] = STRUCT_BUILDS
+        out["rounds"] = struct_rows(a.rounds, stream)
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if not a.no_folds:
         fold_rows(out, dev, stream)
     tlib = ctypes.CDLL(os.path.join(REPO, "tests", "userop", "libhalfadd_tree_op.so"))
