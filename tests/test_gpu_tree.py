@@ -12,7 +12,7 @@ import pytest
 
 import chiara_amd as ca
 import pyoracle as po
-from tree_util import random_program, tree_ref
+from tree_util import all_programs, random_program, tree_ref  # noqa: F401  (all_programs: imported from here too)
 
 pytestmark = pytest.mark.gpu
 
@@ -177,24 +177,6 @@ def test_tree_pair_and_complex_types(gu, dtype, op):
         _run(gu, dtype, op, comb, swaps, 4099, pattern=pat)
         _run(gu, dtype, op, comb, swaps, 257, pattern=pat, off=1)
     _run(gu, dtype, op, *C4_TREE, 8192 + 3, pattern=pat, inplace_leaf=0)
-
-
-def all_programs(nl, max_depth=4):
-    """Every valid post-order program with nl leaves and stack depth <= max_depth."""
-    out = []
-
-    def rec(j, depth, comb):
-        depth += 1
-        if depth > max_depth:
-            return
-        if j == nl - 1:
-            out.append(comb + [depth - 1])
-            return
-        for c in range(0, min(3, depth - 1) + 1):
-            rec(j + 1, depth - c, comb + [c])
-
-    rec(0, 0, [])
-    return out
 
 
 @pytest.mark.parametrize("dtype,op", [(d, o) for d in ("fi", "di", "li", "2i", "si") for o in ("maxloc", "minloc")] +

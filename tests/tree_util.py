@@ -1,6 +1,6 @@
 """Test-side helpers for the fused expression-tree op (chr_reduce_tree): a CPU evaluator of
-the post-order stack program over the oracle's MPI_Reduce_local restatement, and a random
-valid-program generator."""
+the post-order stack program over the oracle's MPI_Reduce_local restatement, the list of
+every valid program and a random valid-program generator."""
 import numpy as np
 
 import pyoracle as po
@@ -25,6 +25,24 @@ def tree_ref(leaves, comb, swaps, dtype, op):
             ci += 1
     assert len(stack) == 1
     return stack[0]
+
+
+def all_programs(nl, max_depth=4):
+    """Every valid post-order program with nl leaves and stack depth <= max_depth."""
+    out = []
+
+    def rec(j, depth, comb):
+        depth += 1
+        if depth > max_depth:
+            return
+        if j == nl - 1:
+            out.append(comb + [depth - 1])
+            return
+        for c in range(0, min(3, depth - 1) + 1):
+            rec(j + 1, depth - c, comb + [c])
+
+    rec(0, 0, [])
+    return out
 
 
 def random_program(rng, nl, max_depth=4):
