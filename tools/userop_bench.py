@@ -22,6 +22,11 @@
    and the trees the register rule keeps from the vector kernel declined to the folds); make -C tests/userop -f
    struct_op.mk all ab.  Only these rows run.
 
+ * --f16: the binary16 SUM of libchiara_ops.so (chiara_amd/ops.py, include/chiara_ops.h) beside the library's own
+   bf16 SUM on the same bytes -- folds m = 1 and 3 at 64 MiB per operand, C4's 8-leaf tree at 16 and 64 MiB per leaf
+   (fraction of 8 TB/s at 9 units) and the C4-shaped 8-virtual-rank allreduce at 128 MiB per rank.  Only these rows
+   run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -209,8 +214,59 @@ def struct_rows(rounds, stream):
     return rows
 
 
+def f16_rows(rounds, stream):
+    """Rows of --f16, per round: the library's bf16 SUM and libchiara_ops.so's f16 SUM back to back on the same
+    buffers (2-byte elements either way; the bits are halves in [0, 1))."""
+    from chiara_amd import ops
+
+    dev = torch.device("cuda:0")
+    variants = [("bf16_sum", ca.BFLOAT16, ca.SUM), ("f16_sum", ops.F16_DTYPE, ops.float16_op(ca.SUM))]
+    rows = [{} for _ in range(rounds)]
+
+    def halves(n):
+        return torch.rand(n, device=dev).to(torch.float16)
+
+    for what, units, mib, reps in ([("fold", m + 1, 64, 60) for m in (1, 3)] + [("tree", 9, 16, 240), ("tree", 9, 64, 80)]):
+        n = (mib << 20) // 2
+        sets = max(1, int(2.25 * (1 << 30)) // (units * 2 * n))
+        bufs = [[halves(n) for _ in range(units)] for _ in range(sets)]
+        for r in range(rounds):
+            for name, dt, op in variants:
+                if what == "fold":  # acc in place, m inputs: m + 2 units of traffic
+                    def go(i, dt=dt, op=op):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_multi(s[0], s[0], s[1:], n, dt, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"fold_m{units - 1}_64MiB_{name}_GBps"] = round((units + 1) * 2 * n / ms / 1e6, 1)
+                else:
+                    def go(i, dt=dt, op=op):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_tree(s[8], s[:8], C4_COMB, C4_SWAPS, n, dt, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"tree8_{mib}MiB_{name}_frac"] = round(9 * 2 * n / (ms * 1e-3) / HBM_PEAK, 4)
+        del bufs
+    nr, cnt = 8, (128 << 20) // 2
+    g = ca.LocalGroup(nr, 0)
+    sends = [halves(cnt) for _ in range(nr)]
+    recvs = [torch.empty(cnt, device=dev, dtype=torch.float16) for _ in range(nr)]
+    for r in range(rounds):
+        for name, dt, op in variants:
+            for _ in range(2):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, dt, op, 4, 4))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, dt, op, 4, 4))
+            torch.cuda.synchronize()
+            rows[r][f"localgroup8_k4b4_128MiB_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+    g.destroy()
+    ops.release()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--no-folds", action="store_true", help="skip the fold rows")
@@ -222,6 +278,15 @@ def main():
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     out = {"tool": "tools/userop_bench.py", "tree_lib": "libhalfadd_tree_op.so"}
+    if a.f16:
+        out = {"tool": "tools/userop_bench.py --f16", "ops_lib": "libchiara_ops.so", "rounds": f16_rows(a.rounds, stream)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.struct:
         out["builds"] = STRUCT_BUILDS
         out["rounds"] = struct_rows(a.rounds, stream)
