@@ -26,7 +26,9 @@ static void run_k_b(const Options& o, Ctx& c, std::ofstream& csv, int k, int cou
         std::fill(recv.begin(), recv.end(), 0);
         if (dev) {
             (void)hipMemset(drecv.p, 0, out_n * es);
-            (void)hipDeviceSynchronize();  // NULL-stream memset vs the comm's non-blocking stream
+            // keeps the memset out of the timed call; for ordering alone it is not needed: the comm's stream is a
+            // blocking stream and orders after NULL-stream work (chiara.h chr_comm_stream, exec_comm.cpp)
+            (void)hipDeviceSynchronize();
         }
         MPI_Barrier(MPI_COMM_WORLD);
         const double t0 = MPI_Wtime();

@@ -7,11 +7,13 @@
 // functor).  Folds go to the launcher as they are; an expression tree (the flat schedules' one-pass evaluation,
 // k_reduce_tree for the predefined ops) goes whole to the op's tree launcher where it registered one
 // (chr_op_create_tree: one HBM pass, inner nodes in registers) and is otherwise, or when that launcher declines,
-// evaluated fold by fold in its post-order program, intermediate values in stream-ordered scratch.  Nothing runs on
-// the host.
+// evaluated fold by fold in its post-order program, intermediate values in scratch kept per stream (TreeScratch).
+// Nothing runs on the host.
 #include "user_ops.hpp"
 
+#include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "chiara.h"
@@ -55,6 +57,82 @@ int call(const UserOp& u, void* out, const void* acc, const void* const* ins, in
     return hip_code(hipGetLastError());
 }
 
+// Scratch of the fold-by-fold trees: one slot per stack position (depth <= 4), kept per stream and reused by the next
+// fold-by-fold tree enqueued on that stream.  Work on one stream runs in order, so the reuse needs no event and no
+// wait.  A hipMallocAsync / hipFreeAsync pair per call kept the call from returning at once: the runtime (ROCm 7.0)
+// hands a freed block back to its stream while the free is still pending, and hipFreeAsync of such a block waits on
+// the host until the stream has drained -- from the second tree enqueued on a busy stream on (measured behind a 19 ms
+// copy: 18.7 ms in that one hipFreeAsync, with the default pool, an own pool, and either with an unlimited release
+// threshold; tests/test_gpu_stream_concurrency.py holds it).  A slot grows by a stream-ordered free and allocation
+// (bytes + 16, so that any residue of `out` fits); the blocks stay with the stream's entry for the life of the
+// process: at most four slots of the largest such tree per stream.  Two calls that are inside user_tree on one stream
+// at once (two host threads, or a launcher that calls back into the library) and hipStreamPerThread, one handle for
+// many streams, take per-call allocations instead.
+struct TreeScratch {
+    void* p[kTreeMaxLeaves] = {};
+    size_t cap[kTreeMaxLeaves] = {};
+    bool busy = false;
+};
+std::mutex g_scratch_mu;
+// The key holds the current device: the NULL stream's handle is the same on every device.  Entries are never erased,
+// so references to them stay valid.
+std::map<std::pair<int, hipStream_t>, TreeScratch> g_scratch;
+
+class ScratchLease {
+  public:
+    explicit ScratchLease(hipStream_t s) : s_(s) {
+        int dev = 0;
+        if (s == hipStreamPerThread || hipGetDevice(&dev) != hipSuccess) return;
+        std::lock_guard<std::mutex> lk(g_scratch_mu);
+        TreeScratch& e = g_scratch[{dev, s}];
+        if (e.busy) return;
+        e.busy = true;
+        mine_ = &e;
+    }
+    ~ScratchLease() {
+        if (!mine_) return;
+        std::lock_guard<std::mutex> lk(g_scratch_mu);
+        mine_->busy = false;
+    }
+    // Slot `pos` with room for `bytes`, or nullptr and the status in *err.
+    void* slot(int pos, size_t bytes, int* err) {
+        if (!mine_) {
+            if (!own_[pos]) *err = hip_code(hipMallocAsync(&own_[pos], bytes, s_));
+            return own_[pos];
+        }
+        if (mine_->cap[pos] < bytes) {
+            if (mine_->p[pos]) {
+                void* old = mine_->p[pos];
+                mine_->p[pos] = nullptr;
+                mine_->cap[pos] = 0;
+                if ((*err = hip_code(hipFreeAsync(old, s_)))) return nullptr;  // behind the calls that used it
+            }
+            if ((*err = hip_code(hipMallocAsync(&mine_->p[pos], bytes, s_)))) {
+                mine_->p[pos] = nullptr;
+                return nullptr;
+            }
+            mine_->cap[pos] = bytes;
+        }
+        return mine_->p[pos];
+    }
+    // The per-call allocations go back in stream order; the stream's own slots stay.
+    int release() {
+        int rc = CHR_SUCCESS;
+        for (void*& q : own_)
+            if (q) {
+                const int e = hip_code(hipFreeAsync(q, s_));
+                if (!rc) rc = e;
+                q = nullptr;
+            }
+        return rc;
+    }
+
+  private:
+    hipStream_t s_;
+    TreeScratch* mine_ = nullptr;
+    void* own_[kTreeMaxLeaves] = {};
+};
+
 // One post-order program (launch_reduce_tree's contract): push leaf j, then comb[j] combines, each popping the top
 // `in` and folding it into the value below -- MPI_Reduce_local(in, below), or with the combine's swap bit
 // MPI_Reduce_local(below, in) (MPICH_do_reduce's order), the running-value-first form of the launcher.  Consecutive
@@ -68,7 +146,7 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
     // A derived type's chunks start at multiples of its size, often off 16-byte alignment; the header's kernels stream
     // operands that are congruent modulo 16, so a slot starts at the residue of `out`.
     const size_t skew = is_derived_type(dtype) ? (uintptr_t)out & 15 : 0;
-    void* slot[kTreeMaxLeaves] = {};  // stack positions: one per leaf at most (tree_program_ok)
+    ScratchLease scratch(s);  // slots by stack position: one per leaf at most (tree_program_ok)
     struct Val {
         const void* p;
         bool leaf;
@@ -90,9 +168,10 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
             if (!out_is_input) dst = out;
         }
         if (!dst) {
-            if (!slot[ch.pos])
-                if (int e = hip_code(hipMallocAsync(&slot[ch.pos], bytes + skew, s))) return e;
-            dst = static_cast<char*>(slot[ch.pos]) + skew;
+            int e = CHR_SUCCESS;
+            void* base = scratch.slot(ch.pos, bytes + 16, &e);
+            if (!base) return e ? e : CHR_ERR_OUT_OF_MEMORY;
+            dst = static_cast<char*>(base) + skew;
         }
         const int e = call(u, dst, ch.acc, ch.ins.data(), (int)ch.ins.size(), n, dtype, ch.rf, s);
         st[ch.pos] = {dst, false};
@@ -122,12 +201,8 @@ int user_tree(const UserOp& u, void* out, const void* const* leaves, int nl, con
     if (!rc) rc = flush(true);
     if (!rc && st.size() == 1 && st[0].p != out)
         rc = hip_code(hipMemcpyAsync(out, st[0].p, bytes, hipMemcpyDeviceToDevice, s));
-    for (void* q : slot)
-        if (q) {
-            const int e = hip_code(hipFreeAsync(q, s));
-            if (!rc) rc = e;
-        }
-    return rc;
+    const int e = scratch.release();
+    return rc ? rc : e;
 }
 
 // Every job with n > 0 and two or more leaves goes to the op's tree launcher in one call, with the residency cap a

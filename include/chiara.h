@@ -141,8 +141,8 @@ int chr_op_free(chr_op op);
 /* ---- user-defined ops, whole expression trees in one pass ------------------------------
  * The flat schedules evaluate each chunk as one expression tree (chr_reduce_tree below).  For a predefined op that
  * is one HBM pass: every leaf read once, the root written once.  Through `fn` alone a user op's tree runs fold by
- * fold, inner nodes in stream-ordered scratch (C4's 8-leaf tree: three launcher calls and 13 units of traffic
- * against 9).  chr_op_create_tree registers, beside `fn`, a launcher that evaluates whole trees itself
+ * fold, inner nodes in scratch the library keeps per stream and reuses in stream order (at most four slots of the
+ * largest such tree; C4's 8-leaf tree: three launcher calls and 13 units of traffic against 9).  chr_op_create_tree registers, beside `fn`, a launcher that evaluates whole trees itself
  * (include/chiara_user_op.hpp builds one from the same device functor: CHR_DEFINE_USER_TREE).  `fn` stays required
  * -- folds, 1-leaf trees and declined calls go through it -- and a NULL `tree_fn` makes the call chr_op_create.  The
  * op comes from the same 64 codes and chr_op_free releases it.
