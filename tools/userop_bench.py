@@ -27,6 +27,12 @@
    (fraction of 8 TB/s at 9 units) and the C4-shaped 8-virtual-rank allreduce at 128 MiB per rank.  Only these rows
    run.
 
+ * --numerics: the struct ops of libchiara_numerics.so (chiara_amd/numerics.py, include/chiara_numerics.h) -- sum2 on
+   float and double pairs (8 and 16 bytes) and moments on double records (24 bytes) -- each beside the library's f32
+   SUM on the same bytes and tests/userop/struct_op.hip's RotMix of the same element size (f32 x 2, f32 x 4, f64 x 3,
+   the shipped build): folds m = 1 and 3 at 64 MiB per operand, C4's 8-leaf tree at 16 and 64 MiB per leaf (fraction
+   of 8 TB/s at 9 units) and the C4-shaped 8-virtual-rank allreduce at 128 MiB per rank.  Only these rows run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -264,8 +270,74 @@ def f16_rows(rounds, stream):
     return rows
 
 
+def numerics_rows(rounds, stream):
+    """Rows of --numerics, per round: for each element size the library's f32 SUM, the RotMix struct op and the
+    numerics op back to back on the same buffers (uniform values in [0, 1): every operation finite)."""
+    from chiara_amd import numerics as num
+
+    dev = torch.device("cuda:0")
+    slib = ctypes.CDLL(os.path.join(REPO, "tests", "userop", STRUCT_BUILDS["shipped"]))
+
+    def rotmix(shape):
+        return ca.op_create(ctypes.cast(getattr(slib, f"chr_struct_RotMixK_{shape}"), ctypes.c_void_p).value,
+                            tree=ctypes.cast(getattr(slib, f"chr_struct_RotMixK_{shape}_tree"), ctypes.c_void_p).value)
+
+    # (label, element bytes, torch type, the op's (dtype, op), RotMix's shape, its base and count)
+    kinds = [("sum2_f32", 8, torch.float32, (num.sum2_type(ca.FLOAT32), num.sum2_op()), "f32x2", ca.FLOAT32, 2),
+             ("sum2_f64", 16, torch.float64, (num.sum2_type(ca.FLOAT64), num.sum2_op()), "f32x4", ca.FLOAT32, 4),
+             ("moments_f64", 24, torch.float64, (num.moments_type(ca.FLOAT64), num.moments_op()), "f64x3", ca.FLOAT64, 3)]
+    rows = [{} for _ in range(rounds)]
+    made = []
+    for label, es, tdt, (dt, op), shape, rbase, rk in kinds:
+        rdt, rop = ca.type_contiguous(rk, rbase), rotmix(shape)
+        made.append((rdt, rop))
+        # (variant, dtype, op, elements per `es` bytes)
+        variants = [("f32_sum", ca.FLOAT32, ca.SUM, es // 4), (f"rotmix_{shape}", rdt, rop, 1), (label, dt, op, 1)]
+        for what, units, mib, reps in ([("fold", m + 1, 64, 60) for m in (1, 3)] + [("tree", 9, 16, 240), ("tree", 9, 64, 80)]):
+            n = (mib << 20) // es
+            sets = max(1, int(2.25 * (1 << 30)) // (units * n * es))
+            bufs = [[torch.rand(n * es // tdt.itemsize, device=dev, dtype=tdt) for _ in range(units)] for _ in range(sets)]
+            for r in range(rounds):
+                for name, vdt, vop, per in variants:
+                    if what == "fold":  # acc in place, m inputs: m + 2 units of traffic
+                        def go(i, vdt=vdt, vop=vop, per=per):
+                            s = bufs[i % sets]
+                            ca.check(ca.reduce_multi(s[0], s[0], s[1:], n * per, vdt, vop, stream))
+                        ms = timed(go, reps)
+                        rows[r][f"fold_m{units - 1}_64MiB_{label}_{name}_GBps"] = round((units + 1) * n * es / ms / 1e6, 1)
+                    else:
+                        def go(i, vdt=vdt, vop=vop, per=per):
+                            s = bufs[i % sets]
+                            ca.check(ca.reduce_tree(s[8], s[:8], C4_COMB, C4_SWAPS, n * per, vdt, vop, stream))
+                        ms = timed(go, reps)
+                        rows[r][f"tree8_{mib}MiB_{label}_{name}_frac"] = round(9 * n * es / (ms * 1e-3) / HBM_PEAK, 4)
+            del bufs
+        nr, cnt = 8, (128 << 20) // es // 8 * 8
+        g = ca.LocalGroup(nr, 0)
+        sends = [torch.rand(cnt * es // tdt.itemsize, device=dev, dtype=tdt) for _ in range(nr)]
+        recvs = [torch.empty(cnt * es // tdt.itemsize, device=dev, dtype=tdt) for _ in range(nr)]
+        for r in range(rounds):
+            for name, vdt, vop, per in variants:
+                for _ in range(2):
+                    ca.check(g.all_reduce_radix_batch(sends, recvs, cnt * per, vdt, vop, 4, 4))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(5):
+                    ca.check(g.all_reduce_radix_batch(sends, recvs, cnt * per, vdt, vop, 4, 4))
+                torch.cuda.synchronize()
+                rows[r][f"localgroup8_k4b4_128MiB_{label}_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+        g.destroy()
+        del sends, recvs
+    for rdt, rop in made:
+        ca.op_free(rop)
+        ca.type_free(rdt)
+    num.release()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
     ap.add_argument("--rounds", type=int, default=2)
@@ -278,6 +350,16 @@ def main():
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     out = {"tool": "tools/userop_bench.py", "tree_lib": "libhalfadd_tree_op.so"}
+    if a.numerics:
+        out = {"tool": "tools/userop_bench.py --numerics", "ops_lib": "libchiara_numerics.so",
+               "struct_lib": STRUCT_BUILDS["shipped"], "rounds": numerics_rows(a.rounds, stream)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.f16:
         out = {"tool": "tools/userop_bench.py --f16", "ops_lib": "libchiara_ops.so", "rounds": f16_rows(a.rounds, stream)}
         line = json.dumps(out)
