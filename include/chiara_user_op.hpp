@@ -60,6 +60,37 @@ struct FoldVec {
 typedef unsigned int tree_w4 __attribute__((ext_vector_type(4)));
 typedef unsigned int tree_w2 __attribute__((ext_vector_type(2)));
 
+// ---- packed combines for 1-byte elements -----------------------------------------------------------------------------
+//
+// A functor over a 1-byte T may also offer
+//     static __device__ uint32_t packed(uint32_t in, uint32_t inout);
+// the combine of the four elements of a word, byte k of the result being operator()(byte k of in, byte k of inout).  The
+// vector loops of k_fold and the vector path of k_tree (TreeApVec) then call it once per word instead of operator()
+// once per byte; the element-wise paths and the tails keep operator().  It is for arithmetic whose conversions come
+// two or four to an instruction (libchiara_fp8.so: csrc/ops/fp8_ops.hip has the measurement).  Detected at compile
+// time: a functor without it compiles exactly as before.
+template <typename F>
+struct HasPacked {
+    template <typename G> static auto test(int) -> decltype(G::packed(0u, 0u), std::true_type{});
+    template <typename G> static std::false_type test(...);
+    static constexpr bool value = decltype(test<F>(0))::value;
+};
+template <typename T, typename F>
+constexpr bool packed_vec() {
+    return sizeof(T) == 1 && HasPacked<F>::value;
+}
+struct PackedWords { uint32_t w[4]; };  // a 16-B vector of 1-byte elements as words
+// r = x o r, or with running_first r o x, on the 16 elements of a vector
+template <typename V, typename F>
+__device__ __forceinline__ void packed_fold(V& r, const V& x, bool running_first) {
+    PackedWords rw = __builtin_bit_cast(PackedWords, r);
+    const PackedWords xw = __builtin_bit_cast(PackedWords, x);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)  // a swapped combine is the plain one on exchanged operands: select them, combine once
+        rw.w[k] = F::packed(running_first ? rw.w[k] : xw.w[k], running_first ? xw.w[k] : rw.w[k]);
+    r = __builtin_bit_cast(V, rw);
+}
+
 // ---- element groups: 16-B vectors for a T whose size S does not divide 16 (a derived type's struct) ---------------
 //
 // A lane's unit of work is a group of G = lcm(S, 16) bytes: V = G / 16 vectors holding E = G / S whole elements (S = 24:
@@ -262,11 +293,16 @@ __global__ void k_fold(FoldArgs a) {
                 V x[kU];
 #pragma unroll
                 for (int u = 0; u < kU; ++u) x[u] = inv[base + (size_t)u * blockDim.x];
+                if constexpr (packed_vec<T, F>()) {
+#pragma unroll
+                    for (int u = 0; u < kU; ++u) packed_fold<V, F>(r[u], x[u], a.running_first != 0);
+                } else {
 #pragma unroll
                 for (int u = 0; u < kU; ++u)
 #pragma unroll
                     for (int e = 0; e < kN; ++e)
                         r[u].e[e] = a.running_first ? f(r[u].e[e], x[u].e[e]) : f(x[u].e[e], r[u].e[e]);
+                }
             }
 #pragma unroll
             for (int u = 0; u < kU; ++u) outv[base + (size_t)u * blockDim.x] = r[u];
@@ -275,8 +311,12 @@ __global__ void k_fold(FoldArgs a) {
             V r = accv[v];
             for (int j = 0; j < a.m; ++j) {
                 const V x = static_cast<const V*>(a.ins[j])[v];
+                if constexpr (packed_vec<T, F>()) {
+                    packed_fold<V, F>(r, x, a.running_first != 0);
+                } else {
 #pragma unroll
                 for (int e = 0; e < kN; ++e) r.e[e] = a.running_first ? f(r.e[e], x.e[e]) : f(x.e[e], r.e[e]);
+                }
             }
             outv[v] = r;
         }
@@ -451,6 +491,12 @@ template <typename T, typename F>
 struct TreeApVec {  // in o run on the 16 / sizeof(T) elements of a vector
     using S = tree_w4;
     __device__ __forceinline__ static S ap(S in, S run) {
+        if constexpr (packed_vec<T, F>()) {  // four elements per call (packed combines, above)
+            S r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = F::packed(in[k], run[k]);
+            return r;
+        }
         using V = FoldVec<T>;
         const V x = __builtin_bit_cast(V, in);
         V r = __builtin_bit_cast(V, run);

@@ -33,6 +33,11 @@
    the shipped build): folds m = 1 and 3 at 64 MiB per operand, C4's 8-leaf tree at 16 and 64 MiB per leaf (fraction
    of 8 TB/s at 9 units) and the C4-shaped 8-virtual-rank allreduce at 128 MiB per rank.  Only these rows run.
 
+ * --fp8: the OCP FP8 SUM of libchiara_fp8.so (chiara_amd/fp8.py, include/chiara_fp8.h) -- E4M3 under each overflow
+   policy and E5M2 under IEEE -- beside the binary16 SUM of libchiara_ops.so on the same bytes: folds m = 1 and 3 at
+   64 MiB per operand and C4's 8-leaf tree at 16 and 64 MiB per leaf (fraction of 8 TB/s at 9 units).  Only these rows
+   run.  --fp8-perbyte LIB.so adds the same SUMs of a build without the packed combines (make fp8_ab).
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -270,6 +275,56 @@ def f16_rows(rounds, stream):
     return rows
 
 
+def fp8_rows(rounds, stream, perbyte=None):
+    """Rows of --fp8, per round: libchiara_ops.so's f16 SUM and the FP8 SUMs back to back on the same buffers (the
+    same bytes either way: every byte below 0x38, so E4M3 and E5M2 codes below 1 and halves below 0.5, every sum finite)."""
+    from chiara_amd import fp8, ops
+
+    dev = torch.device("cuda:0")
+    variants = [("f16_sum", ops.F16_DTYPE, ops.float16_op(ca.SUM), 2),
+                ("e4m3_sum_ieee", fp8.F8_DTYPE, fp8.fp8_op(fp8.E4M3, ca.SUM, fp8.IEEE), 1),
+                ("e4m3_sum_sat", fp8.F8_DTYPE, fp8.fp8_op(fp8.E4M3, ca.SUM, fp8.SATURATE), 1),
+                ("e5m2_sum_ieee", fp8.F8_DTYPE, fp8.fp8_op(fp8.E5M2, ca.SUM, fp8.IEEE), 1)]
+    ab = None
+    if perbyte:  # the same ops of a -DCHR_FP8_PACKED=0 build (make fp8_ab): the per-byte side of the packed A/B
+        ab = ctypes.CDLL(os.path.abspath(perbyte))
+        for name, fmt, o in (("e4m3_sum_ieee", fp8.E4M3, fp8.IEEE), ("e4m3_sum_sat", fp8.E4M3, fp8.SATURATE),
+                             ("e5m2_sum_ieee", fp8.E5M2, fp8.IEEE)):
+            code = ctypes.c_int(0)
+            ca.check(ab.chr_fp8_op(fmt, ca.SUM, o, ctypes.byref(code)))
+            variants.append((f"{name}_perbyte", fp8.F8_DTYPE, code.value, 1))
+    rows = [{} for _ in range(rounds)]
+
+    def codes(nbytes):
+        return torch.randint(0, 0x38, (nbytes,), dtype=torch.uint8, device=dev)
+
+    for what, units, mib, reps in ([("fold", m + 1, 64, 60) for m in (1, 3)] + [("tree", 9, 16, 240), ("tree", 9, 64, 80)]):
+        nbytes = mib << 20
+        sets = max(1, int(2.25 * (1 << 30)) // (units * nbytes))
+        bufs = [[codes(nbytes) for _ in range(units)] for _ in range(sets)]
+        for r in range(rounds):
+            for name, dt, op, es in variants:
+                n = nbytes // es
+                if what == "fold":  # acc in place, m inputs: m + 2 units of traffic
+                    def go(i, dt=dt, op=op, n=n):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_multi(s[0], s[0], s[1:], n, dt, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"fold_m{units - 1}_64MiB_{name}_GBps"] = round((units + 1) * nbytes / ms / 1e6, 1)
+                else:
+                    def go(i, dt=dt, op=op, n=n):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_tree(s[8], s[:8], C4_COMB, C4_SWAPS, n, dt, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"tree8_{mib}MiB_{name}_frac"] = round(9 * nbytes / (ms * 1e-3) / HBM_PEAK, 4)
+        del bufs
+    ops.release()
+    fp8.release()
+    if ab is not None:
+        ab.chr_fp8_release()
+    return rows
+
+
 def numerics_rows(rounds, stream):
     """Rows of --numerics, per round: for each element size the library's f32 SUM, the RotMix struct op and the
     numerics op back to back on the same buffers (uniform values in [0, 1): every operation finite)."""
@@ -337,6 +392,9 @@ def numerics_rows(rounds, stream):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fp8", action="store_true", help="only the FP8 rows of libchiara_fp8.so (see above)")
+    ap.add_argument("--fp8-perbyte", metavar="LIB.so",
+                    help="with --fp8: a -DCHR_FP8_PACKED=0 build of fp8_ops.hip (make fp8_ab); its SUMs as *_perbyte")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -350,6 +408,16 @@ def main():
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     out = {"tool": "tools/userop_bench.py", "tree_lib": "libhalfadd_tree_op.so"}
+    if a.fp8:
+        out = {"tool": "tools/userop_bench.py --fp8", "ops_lib": "libchiara_fp8.so", "f16_lib": "libchiara_ops.so",
+               "perbyte_lib": a.fp8_perbyte and os.path.basename(a.fp8_perbyte), "rounds": fp8_rows(a.rounds, stream, a.fp8_perbyte)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.numerics:
         out = {"tool": "tools/userop_bench.py --numerics", "ops_lib": "libchiara_numerics.so",
                "struct_lib": STRUCT_BUILDS["shipped"], "rounds": numerics_rows(a.rounds, stream)}
