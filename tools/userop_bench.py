@@ -38,6 +38,11 @@
    64 MiB per operand and C4's 8-leaf tree at 16 and 64 MiB per leaf (fraction of 8 TB/s at 9 units).  Only these rows
    run.  --fp8-perbyte LIB.so adds the same SUMs of a build without the packed combines (make fp8_ab).
 
+ * --mx: the MXFP8 block-scaled SUM of libchiara_mx.so (chiara_amd/mx.py, include/chiara_mx.h), E4M3 and E5M2, beside
+   the E4M3 SATURATE SUM of libchiara_fp8.so on the same bytes: folds m = 1 and 3 at the tile count nearest 64 MiB
+   per operand (127 100 tiles of 528 bytes), GB/s against the (m + 2) x bytes of traffic, and the ratio to the FP8
+   SUM.  Only these rows run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -325,6 +330,46 @@ def fp8_rows(rounds, stream, perbyte=None):
     return rows
 
 
+def mx_rows(rounds, stream):
+    """Rows of --mx, per round: libchiara_fp8.so's E4M3 SATURATE SUM and the MX SUMs back to back on the same buffers:
+    tiles quantized from normal samples, every block at a magnitude of its own (as FP8 codes the same bytes are
+    finite values of any size; SATURATE keeps them so)."""
+    from chiara_amd import fp8, mx
+
+    dev = torch.device("cuda:0")
+    tiles = round((64 << 20) / mx.TILE_BYTES)
+    nbytes, nvals = tiles * mx.TILE_BYTES, tiles * mx.TILE_VALUES
+    variants = [("fp8_e4m3_sum_sat", fp8.F8_DTYPE, fp8.fp8_op(fp8.E4M3, ca.SUM, fp8.SATURATE), nbytes),
+                ("mx_e4m3_sum", mx.mx_type(), mx.mx_sum(fp8.E4M3), tiles),
+                ("mx_e5m2_sum", mx.mx_type(), mx.mx_sum(fp8.E5M2), tiles)]
+    rows = [{"tiles": tiles, "bytes_per_operand": nbytes} for _ in range(rounds)]
+
+    def operand():
+        x = torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
+        t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ca.check(mx.quantize(t, x, nvals, ca.FLOAT32, fp8.E4M3, stream))
+        return t
+
+    for m in (1, 3):
+        sets = max(1, int(2.25 * (1 << 30)) // ((m + 1) * nbytes))
+        bufs = [[operand() for _ in range(m + 1)] for _ in range(sets)]
+        torch.cuda.synchronize()
+        for r in range(rounds):
+            for name, dt, op, n in variants:
+                def go(i, dt=dt, op=op, n=n):  # acc in place, m inputs: m + 2 units of traffic
+                    s = bufs[i % sets]
+                    ca.check(ca.reduce_multi(s[0], s[0], s[1:], n, dt, op, stream))
+                ms = timed(go, 60)
+                rows[r][f"fold_m{m}_64MiB_{name}_GBps"] = round((m + 2) * nbytes / ms / 1e6, 1)
+            for f in ("e4m3", "e5m2"):
+                rows[r][f"fold_m{m}_64MiB_mx_{f}_over_fp8"] = round(
+                    rows[r][f"fold_m{m}_64MiB_mx_{f}_sum_GBps"] / rows[r][f"fold_m{m}_64MiB_fp8_e4m3_sum_sat_GBps"], 3)
+        del bufs
+    fp8.release()
+    mx.release()
+    return rows
+
+
 def numerics_rows(rounds, stream):
     """Rows of --numerics, per round: for each element size the library's f32 SUM, the RotMix struct op and the
     numerics op back to back on the same buffers (uniform values in [0, 1): every operation finite)."""
@@ -395,6 +440,7 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="only the FP8 rows of libchiara_fp8.so (see above)")
     ap.add_argument("--fp8-perbyte", metavar="LIB.so",
                     help="with --fp8: a -DCHR_FP8_PACKED=0 build of fp8_ops.hip (make fp8_ab); its SUMs as *_perbyte")
+    ap.add_argument("--mx", action="store_true", help="only the MXFP8 rows of libchiara_mx.so (see above)")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -411,6 +457,16 @@ def main():
     if a.fp8:
         out = {"tool": "tools/userop_bench.py --fp8", "ops_lib": "libchiara_fp8.so", "f16_lib": "libchiara_ops.so",
                "perbyte_lib": a.fp8_perbyte and os.path.basename(a.fp8_perbyte), "rounds": fp8_rows(a.rounds, stream, a.fp8_perbyte)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
+    if a.mx:
+        out = {"tool": "tools/userop_bench.py --mx", "ops_lib": "libchiara_mx.so", "fp8_lib": "libchiara_fp8.so",
+               "rounds": mx_rows(a.rounds, stream)}
         line = json.dumps(out)
         print(line)
         if a.out:
