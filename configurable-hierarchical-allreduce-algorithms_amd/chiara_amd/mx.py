@@ -13,7 +13,11 @@ tiles.  A combine aligns the two scales of a block, adds in f32, and re-encodes 
 block's new amax: partial sums never leave the format's range the way they do under one scale per tensor.  The op
 codes are valid wherever a user-defined op is; any dtype but a live type_contiguous(132, UINT32) and any pointer that
 is not 4-byte aligned is refused (ERR_UNSUPPORTED, nothing enqueued).  The library is loaded on first use and
-registers nothing until asked; there is no fallback: a missing libchiara_mx.so is an error."""
+registers nothing until asked; there is no fallback: a missing libchiara_mx.so is an error.
+
+mx_sum's op carries the fold launcher alone, so the flat schedules' expression trees run fold by fold.
+mx_sum_tree(fmt) is the same SUM with the tree kernel of libchiara_mx_tree.so (include/chiara_mx_tree.h): one HBM
+pass per tree, the same bytes; tree_stats() counts its launcher's calls and tree_release() frees its ops."""
 import ctypes
 import os
 
@@ -91,4 +95,51 @@ def stats(reset=False):
     """(fold-launcher calls, calls it declined, kernels it enqueued) since the last reset (chr_mx_stats)."""
     c = (ctypes.c_long * 3)()
     mx_lib().chr_mx_stats(c, 1 if reset else 0)
+    return tuple(c)
+
+
+# ---- one-pass expression trees: libchiara_mx_tree.so (include/chiara_mx_tree.h) -------------------------------------
+
+MX_TREE_LIB_PATH = os.path.join(HERE, "libchiara_mx_tree.so")
+
+_mx_tree_lib = None
+
+
+def mx_tree_lib():
+    """libchiara_mx_tree.so, loaded on first use (libchiara_mx.so and libchiara.so, its dependencies, are this
+    process's copies)."""
+    global _mx_tree_lib
+    if _mx_tree_lib is None:
+        mx_lib()
+        if not os.path.exists(MX_TREE_LIB_PATH):
+            raise ImportError(f"libchiara_mx_tree.so not found at {MX_TREE_LIB_PATH}; build it with `make -C {PKG_ROOT}` "
+                              f"(hipcc --offload-arch=gfx950) or __graft_entry__.build()")
+        L = ctypes.CDLL(MX_TREE_LIB_PATH)
+        L.chr_mx_sum_tree.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.chr_mx_sum_tree.restype = ctypes.c_int
+        L.chr_mx_tree_release.argtypes = []
+        L.chr_mx_tree_release.restype = ctypes.c_int
+        L.chr_mx_tree_stats.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.c_int]
+        L.chr_mx_tree_stats.restype = None
+        _mx_tree_lib = L
+    return _mx_tree_lib
+
+
+def mx_sum_tree(fmt):
+    """The op code of the same SUM registered with its tree launcher (chr_mx_sum_tree): the flat schedules' expression
+    trees and reduce_tree(_batch) run in one HBM pass, the bytes are mx_sum's.  Another code than mx_sum(fmt)'s, the
+    same until tree_release()."""
+    return _code(mx_tree_lib().chr_mx_sum_tree, "chr_mx_sum_tree", int(fmt))
+
+
+def tree_release():
+    """Free the ops libchiara_mx_tree.so registered (chr_mx_tree_release); returns the status code."""
+    return mx_tree_lib().chr_mx_tree_release()
+
+
+def tree_stats(reset=False):
+    """(tree-launcher calls, calls declined, trees handed over, kernels enqueued) since the last reset
+    (chr_mx_tree_stats)."""
+    c = (ctypes.c_long * 4)()
+    mx_tree_lib().chr_mx_tree_stats(c, 1 if reset else 0)
     return tuple(c)

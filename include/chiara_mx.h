@@ -35,7 +35,8 @@
  * associative: a result depends on the schedule's expression tree.
  *
  * The op is created commutative and carries the fold launcher alone: the flat schedules' expression trees run fold by
- * fold through the library's scratch (chiara.h).  Any dtype other than a live chr_type_contiguous(132, CHR_UINT32),
+ * fold through the library's scratch (chiara.h).  chiara_mx_tree.h (libchiara_mx_tree.so) registers the same SUM with a
+ * tree launcher, one HBM pass per tree and the same bytes.  Any dtype other than a live chr_type_contiguous(132, CHR_UINT32),
  * and any call with a pointer that is not 4-byte aligned, is declined: CHR_ERR_UNSUPPORTED, nothing enqueued.
  * Pointers that are all 16-byte aligned take 16-byte accesses, any others 4-byte ones; the bytes are the same.
  */
@@ -61,6 +62,13 @@ int chr_mx_type(chr_dtype* type);
  * library registers nothing.  A format outside the enum: CHR_ERR_UNSUPPORTED; op == NULL: CHR_ERR_INVALID_ARG.
  * Thread-safe. */
 int chr_mx_sum(chr_fp8_format f, chr_op* op);
+
+/* The fold launchers those ops are registered with (chr_user_reduce_fn; running_first is not looked at), for a caller
+ * that registers them itself: chiara_mx_tree.h pairs them with its tree launchers. */
+int chr_mx_e4m3_sum_fold(void* out, const void* acc, const void* const* ins, int m, size_t n, chr_dtype dtype,
+                         int running_first, hipStream_t stream, void* ctx);
+int chr_mx_e5m2_sum_fold(void* out, const void* acc, const void* const* ins, int m, size_t n, chr_dtype dtype,
+                         int running_first, hipStream_t stream, void* ctx);
 
 /* tiles = Q(src): the n values of src (CHR_FLOAT32 or CHR_BFLOAT16, widened exactly) become ceil(n / 512) whole
  * tiles.  Per block, steps 4 - 7 of SUM with s[i] = src[i] (the sign of a zero is kept) and e = 127: a non-finite

@@ -41,7 +41,12 @@
  * --mx: the MXFP8 block-scaled SUM of libchiara_mx.so (chiara_amd/mx.py, include/chiara_mx.h), E4M3 and E5M2, beside
    the E4M3 SATURATE SUM of libchiara_fp8.so on the same bytes: folds m = 1 and 3 at the tile count nearest 64 MiB
    per operand (127 100 tiles of 528 bytes), GB/s against the (m + 2) x bytes of traffic, and the ratio to the FP8
-   SUM.  Only these rows run.
+   SUM; then trees of 2, 4 and 8 leaves (TREE_PROGS; the 8-leaf one is C4's) through chr_reduce_tree at the tile
+   counts nearest 16 and 64 MiB per leaf (ms, and the fraction of 8 TB/s at leaves + 1 units) and the C4-shaped
+   8-virtual-rank allreduce at 128 MiB per rank, each with the fold-only op (mx.mx_sum: C4's tree is three fold
+   launches and 13 units) and the one-pass op of libchiara_mx_tree.so (mx.mx_sum_tree) back to back; and the E4M3
+   tree launcher called directly on the 8-leaf tree at its own residency cap (wg_per_cu = 0), at 12 per CU and at 28.
+   Only these rows run.
 
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
@@ -344,9 +349,10 @@ def mx_rows(rounds, stream):
                 ("mx_e5m2_sum", mx.mx_type(), mx.mx_sum(fp8.E5M2), tiles)]
     rows = [{"tiles": tiles, "bytes_per_operand": nbytes} for _ in range(rounds)]
 
-    def operand():
+    def operand(tiles=tiles):
+        nvals = tiles * mx.TILE_VALUES
         x = torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
-        t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        t = torch.empty(tiles * mx.TILE_BYTES, dtype=torch.uint8, device=dev)
         ca.check(mx.quantize(t, x, nvals, ca.FLOAT32, fp8.E4M3, stream))
         return t
 
@@ -365,7 +371,65 @@ def mx_rows(rounds, stream):
                 rows[r][f"fold_m{m}_64MiB_mx_{f}_over_fp8"] = round(
                     rows[r][f"fold_m{m}_64MiB_mx_{f}_sum_GBps"] / rows[r][f"fold_m{m}_64MiB_fp8_e4m3_sum_sat_GBps"], 3)
         del bufs
+    # C4's 8-leaf tree: the fold-only op against the one-pass op, interleaved within each round
+    tile_t = mx.mx_type()
+    pairs = [(f, (("folds", mx.mx_sum(c)), ("tree", mx.mx_sum_tree(c)))) for f, c in (("e4m3", fp8.E4M3), ("e5m2", fp8.E5M2))]
+    launcher = mx.mx_tree_lib().chr_mx_e4m3_sum_tree
+    launcher.argtypes = [ctypes.POINTER(UserTree), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    launcher.restype = ctypes.c_int
+    for nl, mib, reps in [(nl, mib, reps) for nl in (2, 4, 8) for mib, reps in ((16, 240), (64, 80))]:
+        comb, swaps = TREE_PROGS[nl]
+        tt = round((mib << 20) / mx.TILE_BYTES)
+        tb = tt * mx.TILE_BYTES
+        sets = max(1, int(2.25 * (1 << 30)) // ((nl + 1) * tb))
+        bufs = [[operand(tt) for _ in range(nl + 1)] for _ in range(sets)]
+        trees = []
+        for s in bufs:
+            t = UserTree()
+            t.out = s[nl].data_ptr()
+            for j in range(nl):
+                t.leaves[j] = s[j].data_ptr()
+                t.comb[j] = comb[j]
+            t.nleaves, t.n = nl, tt
+            trees.append(t)
+        torch.cuda.synchronize()
+        for r in range(rounds):
+            rows[r][f"tree_{mib}MiB_tiles"] = tt
+            for f, ops in pairs:
+                for name, op in ops:
+                    def go(i, op=op):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_tree(s[nl], s[:nl], comb, swaps, tt, tile_t, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"tree{nl}_{mib}MiB_mx_{f}_{name}_ms"] = round(ms, 4)
+                    rows[r][f"tree{nl}_{mib}MiB_mx_{f}_{name}_frac"] = round((nl + 1) * tb / (ms * 1e-3) / HBM_PEAK, 4)
+            for cap in (0, 12, 28) if nl == 8 else ():  # 0: the launcher's own 16 per CU; 28: what the registers allow
+                def go(i, cap=cap):
+                    if launcher(ctypes.byref(trees[i % sets]), 1, tile_t, cap, stream.cuda_stream, None) != 0:
+                        raise RuntimeError("tree launcher declined")
+                ms = timed(go, reps)
+                rows[r][f"tree8_{mib}MiB_mx_e4m3_launcher_cap{cap}_ms"] = round(ms, 4)
+        del bufs, trees
+    # the C4-shaped allreduce, 8 virtual ranks, the tile count nearest 128 MiB per rank
+    nr = 8
+    cnt = round((128 << 20) / mx.TILE_BYTES) // nr * nr
+    g = ca.LocalGroup(nr, 0)
+    sends = [operand(cnt) for _ in range(nr)]
+    recvs = [torch.empty(cnt * mx.TILE_BYTES, dtype=torch.uint8, device=dev) for _ in range(nr)]
+    for r in range(rounds):
+        for f, ops in pairs:
+            for name, op in ops:
+                for _ in range(2):
+                    ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(5):
+                    ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+                torch.cuda.synchronize()
+                rows[r][f"localgroup8_k4b4_128MiB_mx_{f}_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+    g.destroy()
     fp8.release()
+    mx.tree_release()
     mx.release()
     return rows
 
@@ -465,8 +529,8 @@ def main():
                 f.write(line + "\n")
         return
     if a.mx:
-        out = {"tool": "tools/userop_bench.py --mx", "ops_lib": "libchiara_mx.so", "fp8_lib": "libchiara_fp8.so",
-               "rounds": mx_rows(a.rounds, stream)}
+        out = {"tool": "tools/userop_bench.py --mx", "ops_lib": "libchiara_mx.so", "tree_lib": "libchiara_mx_tree.so",
+               "fp8_lib": "libchiara_fp8.so", "rounds": mx_rows(a.rounds, stream)}
         line = json.dumps(out)
         print(line)
         if a.out:
