@@ -34,7 +34,7 @@ inline bool is_tile_type(chr_dtype dt) {
            count == CHR_MX_TILE_BYTES / 4;
 }
 
-// The element format: FP4 (a 272-byte tile) would be a third specialisation and a kLaneValues of its own.
+// The element format.  FP4 (a 272-byte tile) is not a third specialisation: a lane owns a whole block there (mx4_tile.hpp).
 template <int FMT> struct Fmt;
 template <> struct Fmt<kE4M3> {
     static constexpr float kMax = 448.0f;  // 0.875 * 2^9

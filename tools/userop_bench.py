@@ -48,6 +48,11 @@
    tree launcher called directly on the 8-leaf tree at its own residency cap (wg_per_cu = 0), at 12 per CU and at 28.
    Only these rows run.
 
+ * --mx4: the MXFP4 block-scaled SUM of libchiara_mx4.so (chiara_amd/mx4.py, include/chiara_mx4.h) beside the MX E4M3
+   SUM of libchiara_mx.so on the same values: folds m = 1 and 3, in place, at 127 100 tiles per operand (272-byte
+   tiles against 528-byte ones: half the bytes), each variant over an HBM-cold rotation of its own, as GB/s of its
+   (m + 2) x bytes of traffic and as 10^9 values per second.  Only these rows run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -434,6 +439,50 @@ def mx_rows(rounds, stream):
     return rows
 
 
+def mx4_rows(rounds, stream):
+    """Rows of --mx4, per round: the MX E4M3 fold and the MX4 fold back to back, each on tiles quantized from the same
+    kind of normal samples, every block at a magnitude of its own."""
+    from chiara_amd import fp8, mx, mx4
+
+    dev = torch.device("cuda:0")
+    tiles = round((64 << 20) / mx.TILE_BYTES)  # 127 100
+    nvals = tiles * mx.TILE_VALUES
+    assert mx4.TILE_VALUES == mx.TILE_VALUES
+    # (name, tile type, op, bytes per operand, quantize)
+    variants = [("mx_e4m3_sum", mx.mx_type(), mx.mx_sum(fp8.E4M3), tiles * mx.TILE_BYTES,
+                 lambda t, x: mx.quantize(t, x, nvals, ca.FLOAT32, fp8.E4M3, stream)),
+                ("mx4_sum", mx4.mx4_type(), mx4.mx4_sum(), tiles * mx4.TILE_BYTES,
+                 lambda t, x: mx4.quantize(t, x, nvals, ca.FLOAT32, stream))]
+    rows = [{"tiles": tiles, "values_per_operand": nvals} for _ in range(rounds)]
+
+    def operand(nbytes, quantize):
+        x = torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
+        t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ca.check(quantize(t, x))
+        return t
+
+    for m in (1, 3):
+        bufs = {name: [[operand(nbytes, q) for _ in range(m + 1)] for _ in range(max(1, int(2.25 * (1 << 30)) // ((m + 1) * nbytes)))]
+                for name, _, _, nbytes, q in variants}
+        torch.cuda.synchronize()
+        for r in range(rounds):
+            for name, dt, op, nbytes, _ in variants:
+                def go(i, dt=dt, op=op, sets=bufs[name]):  # acc in place, m inputs: m + 2 units of traffic
+                    s = sets[i % len(sets)]
+                    ca.check(ca.reduce_multi(s[0], s[0], s[1:], tiles, dt, op, stream))
+                ms = timed(go, 60)
+                rows[r][f"fold_m{m}_{name}_bytes_per_operand"] = nbytes
+                rows[r][f"fold_m{m}_{name}_GBps"] = round((m + 2) * nbytes / ms / 1e6, 1)
+                rows[r][f"fold_m{m}_{name}_Gvalues_per_s"] = round(nvals / ms / 1e6, 2)
+            for unit in ("GBps", "Gvalues_per_s"):
+                rows[r][f"fold_m{m}_mx4_over_mx_e4m3_{unit}"] = round(
+                    rows[r][f"fold_m{m}_mx4_sum_{unit}"] / rows[r][f"fold_m{m}_mx_e4m3_sum_{unit}"], 3)
+        del bufs
+    mx4.release()
+    mx.release()
+    return rows
+
+
 def numerics_rows(rounds, stream):
     """Rows of --numerics, per round: for each element size the library's f32 SUM, the RotMix struct op and the
     numerics op back to back on the same buffers (uniform values in [0, 1): every operation finite)."""
@@ -505,6 +554,7 @@ def main():
     ap.add_argument("--fp8-perbyte", metavar="LIB.so",
                     help="with --fp8: a -DCHR_FP8_PACKED=0 build of fp8_ops.hip (make fp8_ab); its SUMs as *_perbyte")
     ap.add_argument("--mx", action="store_true", help="only the MXFP8 rows of libchiara_mx.so (see above)")
+    ap.add_argument("--mx4", action="store_true", help="only the MXFP4 rows of libchiara_mx4.so (see above)")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -531,6 +581,16 @@ def main():
     if a.mx:
         out = {"tool": "tools/userop_bench.py --mx", "ops_lib": "libchiara_mx.so", "tree_lib": "libchiara_mx_tree.so",
                "fp8_lib": "libchiara_fp8.so", "rounds": mx_rows(a.rounds, stream)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
+    if a.mx4:
+        out = {"tool": "tools/userop_bench.py --mx4", "ops_lib": "libchiara_mx4.so", "mx_lib": "libchiara_mx.so",
+               "rounds": mx4_rows(a.rounds, stream)}
         line = json.dumps(out)
         print(line)
         if a.out:
