@@ -13,8 +13,12 @@ every count is in tiles: half of chiara_amd.mx's bytes on the wire under the sam
 a block whose scale is 0xFF.  The op code is valid wherever a user-defined op is; any dtype but a live
 type_contiguous(68, UINT32) and any pointer that is not 4-byte aligned is refused (ERR_UNSUPPORTED, nothing enqueued).
 The library is loaded on first use and registers nothing until asked; there is no fallback: a missing
-libchiara_mx4.so is an error.  The op carries the fold launcher alone, so the flat schedules' expression trees run
-fold by fold."""
+libchiara_mx4.so is an error.
+
+mx4_sum's op carries the fold launcher alone, so the flat schedules' expression trees run fold by fold.
+mx4_sum_tree() is the same SUM with the tree kernel of libchiara_mx4_tree.so (include/chiara_mx4_tree.h): one HBM
+pass per tree of up to 31 775 tiles (larger ones and single-fold chains stay with the folds, which measured faster
+there), the same bytes; tree_stats() counts its launcher's calls and tree_release() frees its op."""
 import ctypes
 import os
 
@@ -92,4 +96,51 @@ def stats(reset=False):
     """(fold-launcher calls, calls it declined, kernels it enqueued) since the last reset (chr_mx4_stats)."""
     c = (ctypes.c_long * 3)()
     mx4_lib().chr_mx4_stats(c, 1 if reset else 0)
+    return tuple(c)
+
+
+# ---- one-pass expression trees: libchiara_mx4_tree.so (include/chiara_mx4_tree.h) -----------------------------------
+
+MX4_TREE_LIB_PATH = os.path.join(HERE, "libchiara_mx4_tree.so")
+
+_mx4_tree_lib = None
+
+
+def mx4_tree_lib():
+    """libchiara_mx4_tree.so, loaded on first use (libchiara_mx4.so and libchiara.so, its dependencies, are this
+    process's copies)."""
+    global _mx4_tree_lib
+    if _mx4_tree_lib is None:
+        mx4_lib()
+        if not os.path.exists(MX4_TREE_LIB_PATH):
+            raise ImportError(f"libchiara_mx4_tree.so not found at {MX4_TREE_LIB_PATH}; build it with `make -C {PKG_ROOT}` "
+                              f"(hipcc --offload-arch=gfx950) or __graft_entry__.build()")
+        L = ctypes.CDLL(MX4_TREE_LIB_PATH)
+        L.chr_mx4_sum_tree.argtypes = [ctypes.POINTER(ctypes.c_int)]
+        L.chr_mx4_sum_tree.restype = ctypes.c_int
+        L.chr_mx4_tree_release.argtypes = []
+        L.chr_mx4_tree_release.restype = ctypes.c_int
+        L.chr_mx4_tree_stats.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.c_int]
+        L.chr_mx4_tree_stats.restype = None
+        _mx4_tree_lib = L
+    return _mx4_tree_lib
+
+
+def mx4_sum_tree():
+    """The op code of the same SUM registered with its tree launcher (chr_mx4_sum_tree): the flat schedules' expression
+    trees and reduce_tree(_batch) run in one HBM pass, the bytes are mx4_sum's.  Another code than mx4_sum()'s, the
+    same until tree_release()."""
+    return _code(mx4_tree_lib().chr_mx4_sum_tree, "chr_mx4_sum_tree")
+
+
+def tree_release():
+    """Free the op libchiara_mx4_tree.so registered (chr_mx4_tree_release); returns the status code."""
+    return mx4_tree_lib().chr_mx4_tree_release()
+
+
+def tree_stats(reset=False):
+    """(tree-launcher calls, calls declined, trees handed over, kernels enqueued) since the last reset
+    (chr_mx4_tree_stats)."""
+    c = (ctypes.c_long * 4)()
+    mx4_tree_lib().chr_mx4_tree_stats(c, 1 if reset else 0)
     return tuple(c)

@@ -51,7 +51,17 @@
  * --mx4: the MXFP4 block-scaled SUM of libchiara_mx4.so (chiara_amd/mx4.py, include/chiara_mx4.h) beside the MX E4M3
    SUM of libchiara_mx.so on the same values: folds m = 1 and 3, in place, at 127 100 tiles per operand (272-byte
    tiles against 528-byte ones: half the bytes), each variant over an HBM-cold rotation of its own, as GB/s of its
-   (m + 2) x bytes of traffic and as 10^9 values per second.  Only these rows run.
+   (m + 2) x bytes of traffic and as 10^9 values per second; then trees of 2, 4 and 8 leaves (TREE_PROGS; the 8-leaf
+   one is C4's) through chr_reduce_tree at 31 775 and 127 100 tiles per leaf, the 8-leaf one also at 47 662, 63 550
+   and 95 325, the sizes the launcher's size bound is read from (ms, and the fraction of 8 TB/s at leaves + 1
+   units) and the C4-shaped 8-virtual-rank allreduce at 254 200 tiles per rank, each with the fold-only op
+   (mx4.mx4_sum) and the one-pass op of libchiara_mx4_tree.so (mx4.mx4_sum_tree) back to back; and the tree launcher
+   called directly on the 8-leaf tree at its own residency cap (wg_per_cu = 0), at 12 per CU and at 32, all the
+   waves a CU holds.  The shipped launcher declines single-fold chains and trees beyond its size bound to the folds, so
+   the one-pass tree rows and the direct launcher rows need --mx4-take-all LIB.so, a build that takes every tree (make
+   mx4_tree_ab), registered here with libchiara_mx4.so's fold launcher; without it the tree rows run the shipped op,
+   whose declined trees take the folds, and a direct launcher row whose tree the shipped launcher declines is
+   recorded as null.  The allreduce rows always run the shipped op.  Only these rows run.
 
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
@@ -439,9 +449,9 @@ def mx_rows(rounds, stream):
     return rows
 
 
-def mx4_rows(rounds, stream):
+def mx4_rows(rounds, stream, take_all=None):
     """Rows of --mx4, per round: the MX E4M3 fold and the MX4 fold back to back, each on tiles quantized from the same
-    kind of normal samples, every block at a magnitude of its own."""
+    kind of normal samples, every block at a magnitude of its own; then the tree rows (mx4_tree_rows)."""
     from chiara_amd import fp8, mx, mx4
 
     dev = torch.device("cuda:0")
@@ -478,9 +488,87 @@ def mx4_rows(rounds, stream):
                 rows[r][f"fold_m{m}_mx4_over_mx_e4m3_{unit}"] = round(
                     rows[r][f"fold_m{m}_mx4_sum_{unit}"] / rows[r][f"fold_m{m}_mx_e4m3_sum_{unit}"], 3)
         del bufs
-    mx4.release()
     mx.release()
+    mx4_tree_rows(rows, stream, take_all)
+    mx4.release()
     return rows
+
+
+def mx4_tree_rows(rows, stream, take_all=None):
+    """The tree rows of --mx4, into rows[r]: the fold-only op and the one-pass op interleaved within each round."""
+    from chiara_amd import mx4
+
+    dev = torch.device("cuda:0")
+    tile_t = mx4.mx4_type()
+    fptr = lambda L, name: ctypes.cast(getattr(L, name), ctypes.c_void_p).value
+    taken = mx4.mx4_sum_tree()
+    launcher, tree_op = mx4.mx4_tree_lib().chr_mx4_sum_tree_launch, taken
+    if take_all:  # a -DCHR_MX4_TREE_TAKE_ALL=1 build (make mx4_tree_ab): the same kernels, nothing declined for speed
+        ab = ctypes.CDLL(os.path.abspath(take_all))
+        launcher = ab.chr_mx4_sum_tree_launch
+        tree_op = ca.op_create(fptr(mx4.mx4_lib(), "chr_mx4_sum_fold"), commute=True, tree=fptr(ab, "chr_mx4_sum_tree_launch"))
+    launcher.argtypes = [ctypes.POINTER(UserTree), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    launcher.restype = ctypes.c_int
+
+    def operand(tiles):
+        nvals = tiles * mx4.TILE_VALUES
+        x = torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
+        t = torch.empty(tiles * mx4.TILE_BYTES, dtype=torch.uint8, device=dev)
+        ca.check(mx4.quantize(t, x, nvals, ca.FLOAT32, stream))
+        return t
+
+    shapes = [(nl, tt, reps) for nl in (2, 4, 8) for tt, reps in ((31775, 240), (127100, 80))]
+    shapes += [(8, 47662, 160), (8, 63550, 120), (8, 95325, 100)]  # between the two: where one pass stops paying
+    for nl, tt, reps in shapes:
+        comb, swaps = TREE_PROGS[nl]
+        tb = tt * mx4.TILE_BYTES
+        sets = max(1, int(2.25 * (1 << 30)) // ((nl + 1) * tb))
+        bufs = [[operand(tt) for _ in range(nl + 1)] for _ in range(sets)]
+        trees = []
+        for s in bufs:
+            t = UserTree()
+            t.out = s[nl].data_ptr()
+            for j in range(nl):
+                t.leaves[j] = s[j].data_ptr()
+                t.comb[j] = comb[j]
+            t.nleaves, t.n = nl, tt
+            trees.append(t)
+        torch.cuda.synchronize()
+        ops = [("folds", mx4.mx4_sum()), ("tree", tree_op)]
+        for r in range(len(rows)):
+            for name, op in ops:
+                def go(i, op=op):
+                    s = bufs[i % sets]
+                    ca.check(ca.reduce_tree(s[nl], s[:nl], comb, swaps, tt, tile_t, op, stream))
+                ms = timed(go, reps)
+                rows[r][f"tree{nl}_{tt}tiles_mx4_{name}_ms"] = round(ms, 4)
+                rows[r][f"tree{nl}_{tt}tiles_mx4_{name}_frac"] = round((nl + 1) * tb / (ms * 1e-3) / HBM_PEAK, 4)
+            # 0: the launcher's own 16 per CU; 32: all the waves a CU holds
+            for cap in (0, 12, 32) if nl == 8 and tt in (31775, 127100) else ():
+                def go(i, cap=cap):
+                    return launcher(ctypes.byref(trees[i % sets]), 1, tile_t, cap, stream.cuda_stream, None)
+                took = go(0) == 0  # a launcher that declines has enqueued nothing: the row is null
+                rows[r][f"tree8_{tt}tiles_mx4_launcher_cap{cap}_ms"] = round(timed(go, reps), 4) if took else None
+        del bufs, trees
+    # the C4-shaped allreduce, 8 virtual ranks, 2 x 127 100 tiles per rank
+    nr, cnt = 8, 254200
+    g = ca.LocalGroup(nr, 0)
+    sends = [operand(cnt) for _ in range(nr)]
+    recvs = [torch.empty(cnt * mx4.TILE_BYTES, dtype=torch.uint8, device=dev) for _ in range(nr)]
+    for r in range(len(rows)):
+        for name, op in (("folds", mx4.mx4_sum()), ("tree", taken)):
+            for _ in range(2):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+            torch.cuda.synchronize()
+            rows[r][f"localgroup8_k4b4_{cnt}tiles_mx4_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+    g.destroy()
+    if take_all:
+        ca.op_free(tree_op)
+    mx4.tree_release()
 
 
 def numerics_rows(rounds, stream):
@@ -555,6 +643,9 @@ def main():
                     help="with --fp8: a -DCHR_FP8_PACKED=0 build of fp8_ops.hip (make fp8_ab); its SUMs as *_perbyte")
     ap.add_argument("--mx", action="store_true", help="only the MXFP8 rows of libchiara_mx.so (see above)")
     ap.add_argument("--mx4", action="store_true", help="only the MXFP4 rows of libchiara_mx4.so (see above)")
+    ap.add_argument("--mx4-take-all", metavar="LIB.so",
+                    help="with --mx4: a -DCHR_MX4_TREE_TAKE_ALL=1 build of mx4_tree_ops.hip (make mx4_tree_ab); the "
+                         "one-pass tree rows run its launcher")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -590,7 +681,8 @@ def main():
         return
     if a.mx4:
         out = {"tool": "tools/userop_bench.py --mx4", "ops_lib": "libchiara_mx4.so", "mx_lib": "libchiara_mx.so",
-               "rounds": mx4_rows(a.rounds, stream)}
+               "tree_lib": "libchiara_mx4_tree.so", "take_all_lib": a.mx4_take_all and os.path.basename(a.mx4_take_all),
+               "rounds": mx4_rows(a.rounds, stream, a.mx4_take_all)}
         line = json.dumps(out)
         print(line)
         if a.out:
