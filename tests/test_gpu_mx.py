@@ -40,12 +40,8 @@ def _fold(env, fmt, out, acc, ins, n, rf=0, dt=None):
     return rc
 
 
-@FMT
-@pytest.mark.parametrize("mates", [False, True], ids=["pairs", "with block-mates"])
-def test_operand_domain(env, fmt, mates):
-    """All 65 536 code pairs through one fold, m = 1.  `pairs`: 32 pairs to a block under every scale pair of GAPS.
-    `with block-mates`: one pair per block beside a max code, a subnormal and zeros, which fix the amax so that the
-    pair is renormalised in both directions; the scale pairs of GAPS in turn."""
+def domain_operands(fmt, mates):
+    """(inp, acc) tiles of test_operand_domain; tests/test_mx_host.py puts the same operands to the numpy rule."""
     x, y = np.divmod(np.arange(1 << 16, dtype=np.int64), 256)
     if mates:
         px, py = np.zeros((2, 1 << 16, 32), dtype=np.uint8)
@@ -55,8 +51,16 @@ def test_operand_domain(env, fmt, mates):
     else:
         px, py = np.tile(x.reshape(-1, 32), (len(GAPS), 1)), np.tile(y.reshape(-1, 32), (len(GAPS), 1))
         scales = np.repeat(np.array(GAPS), (1 << 16) // 32, axis=0)
-    inp = mx_ref.join(scales[:, 0].reshape(-1, 16), px)
-    acc = mx_ref.join(scales[:, 1].reshape(-1, 16), py)
+    return mx_ref.join(scales[:, 0].reshape(-1, 16), px), mx_ref.join(scales[:, 1].reshape(-1, 16), py)
+
+
+@FMT
+@pytest.mark.parametrize("mates", [False, True], ids=["pairs", "with block-mates"])
+def test_operand_domain(env, fmt, mates):
+    """All 65 536 code pairs through one fold, m = 1.  `pairs`: 32 pairs to a block under every scale pair of GAPS.
+    `with block-mates`: one pair per block beside a max code, a subnormal and zeros, which fix the amax so that the
+    pair is renormalised in both directions; the scale pairs of GAPS in turn."""
+    inp, acc = domain_operands(fmt, mates)
     out = gu.empty_dev(acc.size).fill_(0xA5)
     assert _fold(env, fmt, out, gu.to_dev(acc), [gu.to_dev(inp)], acc.size // TB) == 0
     _same(gu.from_dev(out, np.uint8), mx_ref.combine(fmt, inp, acc), "operand domain")

@@ -36,10 +36,8 @@ def _fold(env, out, acc, ins, n, rf=0, dt=None):
     return rc
 
 
-@pytest.mark.parametrize("mates", [False, True], ids=["pairs", "with block-mates"])
-def test_operand_domain(env, mates):
-    """All 256 code pairs through one fold, m = 1, under every scale pair of GAPS: 32 pairs to a block, or one pair per
-    block beside a max code, a subnormal and zeros, which fix the amax so that the pair is renormalised both ways."""
+def domain_operands(mates):
+    """(inp, acc) tiles of test_operand_domain; tests/test_mx_host.py puts the same operands to the numpy rule."""
     x, y = np.divmod(np.arange(256, dtype=np.int64), 16)
     if mates:
         px, py = np.zeros((2, 256 * len(GAPS), 32), dtype=np.uint8)
@@ -51,8 +49,14 @@ def test_operand_domain(env, mates):
         scales = np.repeat(np.array(GAPS), 8, axis=0)
     blocks = -(-scales.shape[0] // 16) * 16  # whole tiles: the first blocks again
     px, py, scales = (np.resize(a, (blocks,) + a.shape[1:]) for a in (px, py, scales))
-    inp = mx4_ref.join(scales[:, 0].reshape(-1, 16), px)
-    acc = mx4_ref.join(scales[:, 1].reshape(-1, 16), py)
+    return mx4_ref.join(scales[:, 0].reshape(-1, 16), px), mx4_ref.join(scales[:, 1].reshape(-1, 16), py)
+
+
+@pytest.mark.parametrize("mates", [False, True], ids=["pairs", "with block-mates"])
+def test_operand_domain(env, mates):
+    """All 256 code pairs through one fold, m = 1, under every scale pair of GAPS: 32 pairs to a block, or one pair per
+    block beside a max code, a subnormal and zeros, which fix the amax so that the pair is renormalised both ways."""
+    inp, acc = domain_operands(mates)
     out = gu.empty_dev(acc.size).fill_(0xA5)
     assert _fold(env, out, gu.to_dev(acc), [gu.to_dev(inp)], acc.size // TB) == 0
     _same(gu.from_dev(out, np.uint8), mx4_ref.combine(inp, acc), "operand domain")
