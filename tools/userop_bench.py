@@ -63,6 +63,12 @@
    whose declined trees take the folds, and a direct launcher row whose tree the shipped launcher declines is
    recorded as null.  The allreduce rows always run the shipped op.  Only these rows run.
 
+ * --mx6: the MXFP6 block-scaled SUMs of libchiara_mx6.so (chiara_amd/mx6.py, include/chiara_mx6.h), E2M3 and E3M2,
+   beside the MX E4M3 SUM of libchiara_mx.so and the MX4 SUM of libchiara_mx4.so on the same kind of values: folds
+   m = 1 and 3, in place, at 127 100 tiles per operand (400-byte tiles against 528- and 272-byte ones), each variant
+   over an HBM-cold rotation of its own, the four variants alternating within each round, as GB/s of its
+   (m + 2) x bytes of traffic and as 10^9 values per second.  Only these rows run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -494,6 +500,54 @@ def mx4_rows(rounds, stream, take_all=None):
     return rows
 
 
+def mx6_rows(rounds, stream):
+    """Rows of --mx6, per round: the MX E4M3, MX4, MX6 E2M3 and MX6 E3M2 folds back to back, each on tiles quantized
+    from the same kind of normal samples, every block at a magnitude of its own."""
+    from chiara_amd import fp8, mx, mx4, mx6
+
+    dev = torch.device("cuda:0")
+    tiles = round((64 << 20) / mx.TILE_BYTES)  # 127 100
+    nvals = tiles * mx.TILE_VALUES
+    assert mx6.TILE_VALUES == mx4.TILE_VALUES == mx.TILE_VALUES
+    # (name, tile type, op, bytes per operand, quantize)
+    variants = [("mx_e4m3_sum", mx.mx_type(), mx.mx_sum(fp8.E4M3), tiles * mx.TILE_BYTES,
+                 lambda t, x: mx.quantize(t, x, nvals, ca.FLOAT32, fp8.E4M3, stream)),
+                ("mx4_sum", mx4.mx4_type(), mx4.mx4_sum(), tiles * mx4.TILE_BYTES,
+                 lambda t, x: mx4.quantize(t, x, nvals, ca.FLOAT32, stream))]
+    variants += [(f"mx6_{name}_sum", mx6.mx6_type(), mx6.mx6_sum(fmt), tiles * mx6.TILE_BYTES,
+                  lambda t, x, fmt=fmt: mx6.quantize(t, x, nvals, ca.FLOAT32, fmt, stream))
+                 for name, fmt in (("e2m3", mx6.E2M3), ("e3m2", mx6.E3M2))]
+    rows = [{"tiles": tiles, "values_per_operand": nvals} for _ in range(rounds)]
+
+    def operand(nbytes, quantize):
+        x = torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
+        t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ca.check(quantize(t, x))
+        return t
+
+    for m in (1, 3):
+        bufs = {name: [[operand(nbytes, q) for _ in range(m + 1)] for _ in range(max(1, int(2.25 * (1 << 30)) // ((m + 1) * nbytes)))]
+                for name, _, _, nbytes, q in variants}
+        torch.cuda.synchronize()
+        for r in range(rounds):
+            for name, dt, op, nbytes, _ in variants:
+                def go(i, dt=dt, op=op, sets=bufs[name]):  # acc in place, m inputs: m + 2 units of traffic
+                    s = sets[i % len(sets)]
+                    ca.check(ca.reduce_multi(s[0], s[0], s[1:], tiles, dt, op, stream))
+                ms = timed(go, 60)
+                rows[r][f"fold_m{m}_{name}_bytes_per_operand"] = nbytes
+                rows[r][f"fold_m{m}_{name}_GBps"] = round((m + 2) * nbytes / ms / 1e6, 1)
+                rows[r][f"fold_m{m}_{name}_Gvalues_per_s"] = round(nvals / ms / 1e6, 2)
+            for name in ("mx6_e2m3", "mx6_e3m2"):
+                rows[r][f"fold_m{m}_{name}_over_mx_e4m3_Gvalues_per_s"] = round(
+                    rows[r][f"fold_m{m}_{name}_sum_Gvalues_per_s"] / rows[r][f"fold_m{m}_mx_e4m3_sum_Gvalues_per_s"], 3)
+        del bufs
+    mx.release()
+    mx4.release()
+    mx6.release()
+    return rows
+
+
 def mx4_tree_rows(rows, stream, take_all=None):
     """The tree rows of --mx4, into rows[r]: the fold-only op and the one-pass op interleaved within each round."""
     from chiara_amd import mx4
@@ -646,6 +700,7 @@ def main():
     ap.add_argument("--mx4-take-all", metavar="LIB.so",
                     help="with --mx4: a -DCHR_MX4_TREE_TAKE_ALL=1 build of mx4_tree_ops.hip (make mx4_tree_ab); the "
                          "one-pass tree rows run its launcher")
+    ap.add_argument("--mx6", action="store_true", help="only the MXFP6 rows of libchiara_mx6.so (see above)")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -683,6 +738,16 @@ def main():
         out = {"tool": "tools/userop_bench.py --mx4", "ops_lib": "libchiara_mx4.so", "mx_lib": "libchiara_mx.so",
                "tree_lib": "libchiara_mx4_tree.so", "take_all_lib": a.mx4_take_all and os.path.basename(a.mx4_take_all),
                "rounds": mx4_rows(a.rounds, stream, a.mx4_take_all)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
+    if a.mx6:
+        out = {"tool": "tools/userop_bench.py --mx6", "ops_lib": "libchiara_mx6.so", "mx_lib": "libchiara_mx.so",
+               "mx4_lib": "libchiara_mx4.so", "rounds": mx6_rows(a.rounds, stream)}
         line = json.dumps(out)
         print(line)
         if a.out:
