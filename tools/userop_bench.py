@@ -69,6 +69,14 @@
    over an HBM-cold rotation of its own, the four variants alternating within each round, as GB/s of its
    (m + 2) x bytes of traffic and as 10^9 values per second.  Only these rows run.
 
+ * --mxint8: the MXINT8 block-scaled SUM of libchiara_mxint8.so (chiara_amd/mxint8.py, include/chiara_mxint8.h) beside
+   the MX E4M3 SUM of libchiara_mx.so, which moves the same 528-byte tiles: folds m = 1 and 3, in place, at 127 100
+   tiles per operand, each variant over an HBM-cold rotation of its own, the variants alternating within each round,
+   as GB/s of the (m + 2) x bytes of traffic and as 10^9 values per second, on two sets of data: `close`, tiles
+   quantized from normal samples of one variance, where the gaps between block scales are small, and `wild`, random
+   codes under scales 0, 1, 253, 254, 0xFF and 118 .. 136 with 1/8 zero blocks.  --mxint8-f32 LIB.so adds the fold of a
+   build whose every combine is the f32 one (make mxint8_ab), the A/B of the integer combine.  Only these rows run.
+
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
 + one add per element, like SUM's one add); the fold rows keep tests/userop/halfadd_op.hip or CHR_USEROP_SO."""
@@ -548,6 +556,61 @@ def mx6_rows(rounds, stream):
     return rows
 
 
+def mxint8_rows(rounds, stream, f32_lib=None):
+    """Rows of --mxint8, per round and data set: the MX E4M3 fold, the MXINT8 fold and (f32_lib) the f32-only build's
+    fold back to back."""
+    from chiara_amd import fp8, mx, mxint8
+
+    dev = torch.device("cuda:0")
+    tiles = round((64 << 20) / mx.TILE_BYTES)  # 127 100
+    nvals, nbytes = tiles * mx.TILE_VALUES, tiles * mx.TILE_BYTES
+    assert (mxint8.TILE_VALUES, mxint8.TILE_BYTES) == (mx.TILE_VALUES, mx.TILE_BYTES)
+    # (name, tile type, op, quantize)
+    q8 = lambda t, x: mxint8.quantize(t, x, nvals, ca.FLOAT32, stream)
+    variants = [("mx_e4m3_sum", mx.mx_type(), mx.mx_sum(fp8.E4M3), lambda t, x: mx.quantize(t, x, nvals, ca.FLOAT32, fp8.E4M3, stream)),
+                ("mxint8_sum", mxint8.mxint8_type(), mxint8.mxint8_sum(), q8)]
+    ab_op = None
+    if f32_lib:  # a -DCHR_MXI8_INT=0 build (make mxint8_ab): the same kernels without the integer combine
+        ab = ctypes.CDLL(os.path.abspath(f32_lib))
+        ab_op = ca.op_create(ctypes.cast(ab.chr_mxi8_sum_fold, ctypes.c_void_p).value, commute=True)
+        variants.append(("mxint8_f32_sum", mxint8.mxint8_type(), ab_op, q8))
+    rows = [{"tiles": tiles, "values_per_operand": nvals, "bytes_per_operand": nbytes} for _ in range(rounds)]
+    pool = torch.tensor([0, 0, 1, 254, 254, 253, 0xFF] + list(range(118, 137)), dtype=torch.uint8, device=dev)
+
+    def operand(data, quantize):
+        if data == "close":
+            t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ca.check(quantize(t, torch.randn(nvals, device=dev)))
+            return t
+        codes = torch.randint(0, 256, (tiles, 16, 32), dtype=torch.uint8, device=dev)
+        codes[torch.randint(0, 8, (tiles, 16), device=dev) == 0] = 0
+        scales = pool[torch.randint(0, pool.numel(), (tiles, 16), device=dev)]
+        return torch.cat([scales, codes.view(tiles, 512)], dim=1).reshape(-1)
+
+    for data in ("close", "wild"):
+        for m in (1, 3):
+            nsets = max(1, int(2.25 * (1 << 30)) // ((m + 1) * nbytes))
+            bufs = {name: [[operand(data, q) for _ in range(m + 1)] for _ in range(nsets)] for name, _, _, q in variants}
+            torch.cuda.synchronize()
+            for r in range(rounds):
+                for name, dt, op, _ in variants:
+                    def go(i, dt=dt, op=op, sets=bufs[name]):  # acc in place, m inputs: m + 2 units of traffic
+                        s = sets[i % len(sets)]
+                        ca.check(ca.reduce_multi(s[0], s[0], s[1:], tiles, dt, op, stream))
+                    ms = timed(go, 60)
+                    rows[r][f"{data}_fold_m{m}_{name}_GBps"] = round((m + 2) * nbytes / ms / 1e6, 1)
+                    rows[r][f"{data}_fold_m{m}_{name}_Gvalues_per_s"] = round(nvals / ms / 1e6, 2)
+                for name, _, _, _ in variants[1:]:
+                    rows[r][f"{data}_fold_m{m}_{name[:-4]}_over_mx_e4m3"] = round(
+                        rows[r][f"{data}_fold_m{m}_{name}_GBps"] / rows[r][f"{data}_fold_m{m}_mx_e4m3_sum_GBps"], 3)
+            del bufs
+    if ab_op is not None:
+        ca.op_free(ab_op)
+    mx.release()
+    mxint8.release()
+    return rows
+
+
 def mx4_tree_rows(rows, stream, take_all=None):
     """The tree rows of --mx4, into rows[r]: the fold-only op and the one-pass op interleaved within each round."""
     from chiara_amd import mx4
@@ -701,6 +764,9 @@ def main():
                     help="with --mx4: a -DCHR_MX4_TREE_TAKE_ALL=1 build of mx4_tree_ops.hip (make mx4_tree_ab); the "
                          "one-pass tree rows run its launcher")
     ap.add_argument("--mx6", action="store_true", help="only the MXFP6 rows of libchiara_mx6.so (see above)")
+    ap.add_argument("--mxint8", action="store_true", help="only the MXINT8 rows of libchiara_mxint8.so (see above)")
+    ap.add_argument("--mxint8-f32", metavar="LIB.so",
+                    help="with --mxint8: a -DCHR_MXI8_INT=0 build of mxint8_ops.hip (make mxint8_ab); its fold as mxint8_f32")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -748,6 +814,16 @@ def main():
     if a.mx6:
         out = {"tool": "tools/userop_bench.py --mx6", "ops_lib": "libchiara_mx6.so", "mx_lib": "libchiara_mx.so",
                "mx4_lib": "libchiara_mx4.so", "rounds": mx6_rows(a.rounds, stream)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
+    if a.mxint8:
+        out = {"tool": "tools/userop_bench.py --mxint8", "ops_lib": "libchiara_mxint8.so", "mx_lib": "libchiara_mx.so",
+               "f32_lib": a.mxint8_f32 and os.path.basename(a.mxint8_f32), "rounds": mxint8_rows(a.rounds, stream, a.mxint8_f32)}
         line = json.dumps(out)
         print(line)
         if a.out:
