@@ -15,7 +15,10 @@ is valid wherever a user-defined op is; any dtype but a live type_contiguous(132
 4-byte aligned is refused (ERR_UNSUPPORTED, nothing enqueued).  The library is loaded on first use and registers
 nothing until asked; there is no fallback: a missing libchiara_mxint8.so is an error.
 
-mxint8_sum's op carries the fold launcher alone, so the flat schedules' expression trees run fold by fold."""
+mxint8_sum's op carries the fold launcher alone, so the flat schedules' expression trees run fold by fold.
+mxint8_sum_tree() is the same SUM with the tree kernel of libchiara_mxint8_tree.so (include/chiara_mxint8_tree.h): one
+HBM pass per tree (single-fold chains stay with the folds), the same bytes; tree_stats() counts its launcher's calls
+and tree_release() frees its op."""
 import ctypes
 import os
 
@@ -92,4 +95,51 @@ def stats(reset=False):
     """(fold-launcher calls, calls it declined, kernels it enqueued) since the last reset (chr_mxi8_stats)."""
     c = (ctypes.c_long * 3)()
     mxint8_lib().chr_mxi8_stats(c, 1 if reset else 0)
+    return tuple(c)
+
+
+# ---- one-pass expression trees: libchiara_mxint8_tree.so (include/chiara_mxint8_tree.h) -----------------------------
+
+MXINT8_TREE_LIB_PATH = os.path.join(HERE, "libchiara_mxint8_tree.so")
+
+_mxint8_tree_lib = None
+
+
+def mxint8_tree_lib():
+    """libchiara_mxint8_tree.so, loaded on first use (libchiara_mxint8.so and libchiara.so, its dependencies, are this
+    process's copies)."""
+    global _mxint8_tree_lib
+    if _mxint8_tree_lib is None:
+        mxint8_lib()
+        if not os.path.exists(MXINT8_TREE_LIB_PATH):
+            raise ImportError(f"libchiara_mxint8_tree.so not found at {MXINT8_TREE_LIB_PATH}; build it with "
+                              f"`make -C {PKG_ROOT}` (hipcc --offload-arch=gfx950) or __graft_entry__.build()")
+        L = ctypes.CDLL(MXINT8_TREE_LIB_PATH)
+        L.chr_mxi8_sum_tree.argtypes = [ctypes.POINTER(ctypes.c_int)]
+        L.chr_mxi8_sum_tree.restype = ctypes.c_int
+        L.chr_mxi8_tree_release.argtypes = []
+        L.chr_mxi8_tree_release.restype = ctypes.c_int
+        L.chr_mxi8_tree_stats.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.c_int]
+        L.chr_mxi8_tree_stats.restype = None
+        _mxint8_tree_lib = L
+    return _mxint8_tree_lib
+
+
+def mxint8_sum_tree():
+    """The op code of the same SUM registered with its tree launcher (chr_mxi8_sum_tree): the flat schedules'
+    expression trees and reduce_tree(_batch) run in one HBM pass, the bytes are mxint8_sum's.  Another code than
+    mxint8_sum()'s, the same until tree_release()."""
+    return _code(mxint8_tree_lib().chr_mxi8_sum_tree, "chr_mxi8_sum_tree")
+
+
+def tree_release():
+    """Free the op libchiara_mxint8_tree.so registered (chr_mxi8_tree_release); returns the status code."""
+    return mxint8_tree_lib().chr_mxi8_tree_release()
+
+
+def tree_stats(reset=False):
+    """(tree-launcher calls, calls declined, trees handed over, kernels enqueued) since the last reset
+    (chr_mxi8_tree_stats)."""
+    c = (ctypes.c_long * 4)()
+    mxint8_tree_lib().chr_mxi8_tree_stats(c, 1 if reset else 0)
     return tuple(c)

@@ -75,7 +75,15 @@
    as GB/s of the (m + 2) x bytes of traffic and as 10^9 values per second, on two sets of data: `close`, tiles
    quantized from normal samples of one variance, where the gaps between block scales are small, and `wild`, random
    codes under scales 0, 1, 253, 254, 0xFF and 118 .. 136 with 1/8 zero blocks.  --mxint8-f32 LIB.so adds the fold of a
-   build whose every combine is the f32 one (make mxint8_ab), the A/B of the integer combine.  Only these rows run.
+   build whose every combine is the f32 one (make mxint8_ab), the A/B of the integer combine.  Then, on both data
+   sets, trees of 2, 4 and 8 leaves (TREE_PROGS; the 8-leaf one is C4's) through chr_reduce_tree at 31 775 and 127 100
+   tiles per leaf, the 8-leaf one also at 47 662, 63 550 and 95 325 (ms, and the fraction of 8 TB/s at leaves + 1
+   units), and the C4-shaped 8-virtual-rank allreduce at 254 200 tiles per rank on close data, each with the fold-only
+   op (mxint8.mxint8_sum) and the one-pass op of libchiara_mxint8_tree.so (mxint8.mxint8_sum_tree) back to back; and
+   the tree launcher called directly on the 8-leaf tree at its own residency cap (wg_per_cu = 0), at 12, 16 and 28 per
+   CU.  The shipped launcher declines single-fold chains to the folds, so the one-pass rows of the 2-leaf tree and
+   the 4-leaf chain need --mxint8-take-all LIB.so, a build that takes every tree (make mxint8_tree_ab), registered here
+   with libchiara_mxint8.so's fold launcher; the allreduce rows always run the shipped op.  Only these rows run.
 
 The C4 and tree rows run in --rounds alternating rounds in one process (variants interleaved within a round), each
 shape warmed before its timed window.  Measurement tool; the user op is tests/userop/halfadd_tree_op.hip (one mul
@@ -556,9 +564,24 @@ def mx6_rows(rounds, stream):
     return rows
 
 
-def mxint8_rows(rounds, stream, f32_lib=None):
+def mx8_operand(data, tiles, quantize):
+    """`tiles` 528-byte tiles of --mxint8's data set `data`: close, quantize(t, x) of normal samples of one variance;
+    wild, random codes under scales 0, 1, 253, 254, 0xFF and 118 .. 136 with 1/8 zero blocks."""
+    dev = torch.device("cuda:0")
+    if data == "close":
+        t = torch.empty(tiles * 528, dtype=torch.uint8, device=dev)
+        ca.check(quantize(t, torch.randn(tiles * 512, device=dev)))
+        return t
+    pool = torch.tensor([0, 0, 1, 254, 254, 253, 0xFF] + list(range(118, 137)), dtype=torch.uint8, device=dev)
+    codes = torch.randint(0, 256, (tiles, 16, 32), dtype=torch.uint8, device=dev)
+    codes[torch.randint(0, 8, (tiles, 16), device=dev) == 0] = 0
+    scales = pool[torch.randint(0, pool.numel(), (tiles, 16), device=dev)]
+    return torch.cat([scales, codes.view(tiles, 512)], dim=1).reshape(-1)
+
+
+def mxint8_rows(rounds, stream, f32_lib=None, take_all=None):
     """Rows of --mxint8, per round and data set: the MX E4M3 fold, the MXINT8 fold and (f32_lib) the f32-only build's
-    fold back to back."""
+    fold back to back; then the tree rows (mxint8_tree_rows)."""
     from chiara_amd import fp8, mx, mxint8
 
     dev = torch.device("cuda:0")
@@ -575,22 +598,11 @@ def mxint8_rows(rounds, stream, f32_lib=None):
         ab_op = ca.op_create(ctypes.cast(ab.chr_mxi8_sum_fold, ctypes.c_void_p).value, commute=True)
         variants.append(("mxint8_f32_sum", mxint8.mxint8_type(), ab_op, q8))
     rows = [{"tiles": tiles, "values_per_operand": nvals, "bytes_per_operand": nbytes} for _ in range(rounds)]
-    pool = torch.tensor([0, 0, 1, 254, 254, 253, 0xFF] + list(range(118, 137)), dtype=torch.uint8, device=dev)
-
-    def operand(data, quantize):
-        if data == "close":
-            t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ca.check(quantize(t, torch.randn(nvals, device=dev)))
-            return t
-        codes = torch.randint(0, 256, (tiles, 16, 32), dtype=torch.uint8, device=dev)
-        codes[torch.randint(0, 8, (tiles, 16), device=dev) == 0] = 0
-        scales = pool[torch.randint(0, pool.numel(), (tiles, 16), device=dev)]
-        return torch.cat([scales, codes.view(tiles, 512)], dim=1).reshape(-1)
-
     for data in ("close", "wild"):
         for m in (1, 3):
             nsets = max(1, int(2.25 * (1 << 30)) // ((m + 1) * nbytes))
-            bufs = {name: [[operand(data, q) for _ in range(m + 1)] for _ in range(nsets)] for name, _, _, q in variants}
+            bufs = {name: [[mx8_operand(data, tiles, q) for _ in range(m + 1)] for _ in range(nsets)]
+                    for name, _, _, q in variants}
             torch.cuda.synchronize()
             for r in range(rounds):
                 for name, dt, op, _ in variants:
@@ -607,8 +619,82 @@ def mxint8_rows(rounds, stream, f32_lib=None):
     if ab_op is not None:
         ca.op_free(ab_op)
     mx.release()
+    mxint8_tree_rows(rows, stream, take_all)
     mxint8.release()
     return rows
+
+
+def mxint8_tree_rows(rows, stream, take_all=None):
+    """The tree rows of --mxint8, into rows[r]: the fold-only op and the one-pass op interleaved within each round."""
+    from chiara_amd import mxint8
+
+    dev = torch.device("cuda:0")
+    tile_t = mxint8.mxint8_type()
+    fptr = lambda L, name: ctypes.cast(getattr(L, name), ctypes.c_void_p).value
+    taken = mxint8.mxint8_sum_tree()
+    launcher, tree_op = mxint8.mxint8_tree_lib().chr_mxi8_sum_tree_launch, taken
+    if take_all:  # a -DCHR_MXI8_TREE_TAKE_ALL=1 build (make mxint8_tree_ab): the same kernels, nothing declined for speed
+        ab = ctypes.CDLL(os.path.abspath(take_all))
+        launcher = ab.chr_mxi8_sum_tree_launch
+        tree_op = ca.op_create(fptr(mxint8.mxint8_lib(), "chr_mxi8_sum_fold"), commute=True,
+                               tree=fptr(ab, "chr_mxi8_sum_tree_launch"))
+    launcher.argtypes = [ctypes.POINTER(UserTree), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    launcher.restype = ctypes.c_int
+    operand = lambda data, tiles: mx8_operand(
+        data, tiles, lambda t, x: mxint8.quantize(t, x, tiles * mxint8.TILE_VALUES, ca.FLOAT32, stream))
+
+    shapes = [(nl, tt, reps) for nl in (2, 4, 8) for tt, reps in ((31775, 240), (127100, 80))]
+    shapes += [(8, 47662, 160), (8, 63550, 120), (8, 95325, 100)]  # --mx4's sizes between the two
+    for data in ("close", "wild"):
+        for nl, tt, reps in shapes:
+            comb, swaps = TREE_PROGS[nl]
+            tb = tt * mxint8.TILE_BYTES
+            sets = max(1, int(2.25 * (1 << 30)) // ((nl + 1) * tb))
+            bufs = [[operand(data, tt) for _ in range(nl + 1)] for _ in range(sets)]
+            trees = []
+            for s in bufs:
+                t = UserTree()
+                t.out = s[nl].data_ptr()
+                for j in range(nl):
+                    t.leaves[j] = s[j].data_ptr()
+                    t.comb[j] = comb[j]
+                t.nleaves, t.n = nl, tt
+                trees.append(t)
+            torch.cuda.synchronize()
+            for r in range(len(rows)):
+                for name, op in (("folds", mxint8.mxint8_sum()), ("tree", tree_op)):
+                    def go(i, op=op):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_tree(s[nl], s[:nl], comb, swaps, tt, tile_t, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"{data}_tree{nl}_{tt}tiles_mxint8_{name}_ms"] = round(ms, 4)
+                    rows[r][f"{data}_tree{nl}_{tt}tiles_mxint8_{name}_frac"] = round((nl + 1) * tb / (ms * 1e-3) / HBM_PEAK, 4)
+                # 0: the launcher's own 16 per CU; 12: what the library asks for beside RCCL; 28: all 68 VGPRs allow
+                for cap in (0, 12, 16, 28) if nl == 8 and tt in (31775, 127100) else ():
+                    def go(i, cap=cap):
+                        return launcher(ctypes.byref(trees[i % sets]), 1, tile_t, cap, stream.cuda_stream, None)
+                    took = go(0) == 0  # a launcher that declines has enqueued nothing: the row is null
+                    rows[r][f"{data}_tree8_{tt}tiles_mxint8_launcher_cap{cap}_ms"] = round(timed(go, reps), 4) if took else None
+            del bufs, trees
+    # the C4-shaped allreduce, 8 virtual ranks, 2 x 127 100 tiles per rank (eight 31 775-tile trees to a call), close data
+    nr, cnt = 8, 254200
+    g = ca.LocalGroup(nr, 0)
+    sends = [operand("close", cnt) for _ in range(nr)]
+    recvs = [torch.empty(cnt * mxint8.TILE_BYTES, dtype=torch.uint8, device=dev) for _ in range(nr)]
+    for r in range(len(rows)):
+        for name, op in (("folds", mxint8.mxint8_sum()), ("tree", taken)):
+            for _ in range(2):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+            torch.cuda.synchronize()
+            rows[r][f"localgroup8_k4b4_{cnt}tiles_mxint8_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+    g.destroy()
+    if take_all:
+        ca.op_free(tree_op)
+    mxint8.tree_release()
 
 
 def mx4_tree_rows(rows, stream, take_all=None):
@@ -767,6 +853,9 @@ def main():
     ap.add_argument("--mxint8", action="store_true", help="only the MXINT8 rows of libchiara_mxint8.so (see above)")
     ap.add_argument("--mxint8-f32", metavar="LIB.so",
                     help="with --mxint8: a -DCHR_MXI8_INT=0 build of mxint8_ops.hip (make mxint8_ab); its fold as mxint8_f32")
+    ap.add_argument("--mxint8-take-all", metavar="LIB.so",
+                    help="with --mxint8: a -DCHR_MXI8_TREE_TAKE_ALL=1 build of mxint8_tree_ops.hip (make mxint8_tree_ab); "
+                         "the one-pass tree rows run its launcher")
     ap.add_argument("--numerics", action="store_true", help="only the struct-op rows of libchiara_numerics.so (see above)")
     ap.add_argument("--f16", action="store_true", help="only the binary16 rows (see above)")
     ap.add_argument("--struct", action="store_true", help="only the derived-type rows (see above)")
@@ -823,7 +912,9 @@ def main():
         return
     if a.mxint8:
         out = {"tool": "tools/userop_bench.py --mxint8", "ops_lib": "libchiara_mxint8.so", "mx_lib": "libchiara_mx.so",
-               "f32_lib": a.mxint8_f32 and os.path.basename(a.mxint8_f32), "rounds": mxint8_rows(a.rounds, stream, a.mxint8_f32)}
+               "f32_lib": a.mxint8_f32 and os.path.basename(a.mxint8_f32), "tree_lib": "libchiara_mxint8_tree.so",
+               "take_all_lib": a.mxint8_take_all and os.path.basename(a.mxint8_take_all),
+               "rounds": mxint8_rows(a.rounds, stream, a.mxint8_f32, a.mxint8_take_all)}
         line = json.dumps(out)
         print(line)
         if a.out:
