@@ -16,7 +16,10 @@ type_contiguous(100, UINT32) and any pointer that is not 4-byte aligned is refus
 The library is loaded on first use and registers nothing until asked; there is no fallback: a missing
 libchiara_mx6.so is an error.
 
-mx6_sum's ops carry the fold launcher alone, so the flat schedules' expression trees run fold by fold."""
+mx6_sum's ops carry the fold launcher alone, so the flat schedules' expression trees run fold by fold.
+mx6_sum_tree(fmt) is the same SUM with the tree kernel of libchiara_mx6_tree.so (include/chiara_mx6_tree.h): one HBM
+pass per tree (single-fold chains stay with the folds), the same bytes; tree_stats() counts its launchers' calls and
+tree_release() frees its ops."""
 import ctypes
 import os
 
@@ -96,4 +99,51 @@ def stats(reset=False):
     """(fold-launcher calls, calls they declined, kernels they enqueued) since the last reset (chr_mx6_stats)."""
     c = (ctypes.c_long * 3)()
     mx6_lib().chr_mx6_stats(c, 1 if reset else 0)
+    return tuple(c)
+
+
+# ---- one-pass expression trees: libchiara_mx6_tree.so (include/chiara_mx6_tree.h) -----------------------------------
+
+MX6_TREE_LIB_PATH = os.path.join(HERE, "libchiara_mx6_tree.so")
+
+_mx6_tree_lib = None
+
+
+def mx6_tree_lib():
+    """libchiara_mx6_tree.so, loaded on first use (libchiara_mx6.so and libchiara.so, its dependencies, are this
+    process's copies)."""
+    global _mx6_tree_lib
+    if _mx6_tree_lib is None:
+        mx6_lib()
+        if not os.path.exists(MX6_TREE_LIB_PATH):
+            raise ImportError(f"libchiara_mx6_tree.so not found at {MX6_TREE_LIB_PATH}; build it with "
+                              f"`make -C {PKG_ROOT}` (hipcc --offload-arch=gfx950) or __graft_entry__.build()")
+        L = ctypes.CDLL(MX6_TREE_LIB_PATH)
+        L.chr_mx6_sum_tree.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.chr_mx6_sum_tree.restype = ctypes.c_int
+        L.chr_mx6_tree_release.argtypes = []
+        L.chr_mx6_tree_release.restype = ctypes.c_int
+        L.chr_mx6_tree_stats.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.c_int]
+        L.chr_mx6_tree_stats.restype = None
+        _mx6_tree_lib = L
+    return _mx6_tree_lib
+
+
+def mx6_sum_tree(fmt):
+    """The op code of the same SUM on tiles of format `fmt` registered with its tree launcher (chr_mx6_sum_tree): the
+    flat schedules' expression trees and reduce_tree(_batch) run in one HBM pass, the bytes are mx6_sum(fmt)'s.
+    Another code than mx6_sum(fmt)'s, the same until tree_release()."""
+    return _code(mx6_tree_lib().chr_mx6_sum_tree, "chr_mx6_sum_tree", int(fmt))
+
+
+def tree_release():
+    """Free the ops libchiara_mx6_tree.so registered (chr_mx6_tree_release); returns the status code."""
+    return mx6_tree_lib().chr_mx6_tree_release()
+
+
+def tree_stats(reset=False):
+    """(tree-launcher calls, calls declined, trees handed over, kernels enqueued) since the last reset, both formats
+    together (chr_mx6_tree_stats)."""
+    c = (ctypes.c_long * 4)()
+    mx6_tree_lib().chr_mx6_tree_stats(c, 1 if reset else 0)
     return tuple(c)

@@ -43,7 +43,7 @@
  * give the same bytes.  It is not associative: a result depends on the schedule's expression tree.
  *
  * The ops are created commutative and carry the fold launcher alone: the flat schedules' expression trees run fold by
- * fold through the library's scratch (chiara.h).  Any dtype other than a live chr_type_contiguous(100, CHR_UINT32), and
+ * fold through the library's scratch (chiara.h); chiara_mx6_tree.h has the same SUMs with one-pass trees.  Any dtype other than a live chr_type_contiguous(100, CHR_UINT32), and
  * any call with a pointer that is not 4-byte aligned, is declined: CHR_ERR_UNSUPPORTED, nothing enqueued.  A block
  * lies at byte 16 + 24 b of its tile, 8-byte aligned whenever the buffer is: pointers that are all 8-byte aligned take
  * 8-byte accesses, any others 4-byte ones; the bytes are the same.

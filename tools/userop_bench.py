@@ -67,7 +67,15 @@
    beside the MX E4M3 SUM of libchiara_mx.so and the MX4 SUM of libchiara_mx4.so on the same kind of values: folds
    m = 1 and 3, in place, at 127 100 tiles per operand (400-byte tiles against 528- and 272-byte ones), each variant
    over an HBM-cold rotation of its own, the four variants alternating within each round, as GB/s of its
-   (m + 2) x bytes of traffic and as 10^9 values per second.  Only these rows run.
+   (m + 2) x bytes of traffic and as 10^9 values per second.  Then, per format, trees of 2, 4 and 8 leaves (TREE_PROGS;
+   the 8-leaf one is C4's) through chr_reduce_tree at 31 775 and 127 100 tiles per leaf, the 8-leaf one also at
+   47 662, 63 550 and 95 325 (ms, and the fraction of 8 TB/s at leaves + 1 units), and the C4-shaped 8-virtual-rank
+   allreduce at 254 200 tiles per rank, each with the fold-only op (mx6.mx6_sum) and the one-pass op of
+   libchiara_mx6_tree.so (mx6.mx6_sum_tree) back to back; and the tree launcher called directly on the 8-leaf tree at
+   its own residency cap (wg_per_cu = 0), at 12, 16 and 26 per CU, the most its LDS stack allows.  The shipped
+   launchers decline single-fold chains to the folds, so the one-pass rows of the 2-leaf tree and the 4-leaf chain need
+   --mx6-take-all LIB.so, a build that takes every tree (make mx6_tree_ab), registered here with libchiara_mx6.so's
+   fold launchers; the allreduce rows always run the shipped ops.  Only these rows run.
 
  * --mxint8: the MXINT8 block-scaled SUM of libchiara_mxint8.so (chiara_amd/mxint8.py, include/chiara_mxint8.h) beside
    the MX E4M3 SUM of libchiara_mx.so, which moves the same 528-byte tiles: folds m = 1 and 3, in place, at 127 100
@@ -516,9 +524,9 @@ def mx4_rows(rounds, stream, take_all=None):
     return rows
 
 
-def mx6_rows(rounds, stream):
+def mx6_rows(rounds, stream, take_all=None):
     """Rows of --mx6, per round: the MX E4M3, MX4, MX6 E2M3 and MX6 E3M2 folds back to back, each on tiles quantized
-    from the same kind of normal samples, every block at a magnitude of its own."""
+    from the same kind of normal samples, every block at a magnitude of its own; then the tree rows (mx6_tree_rows)."""
     from chiara_amd import fp8, mx, mx4, mx6
 
     dev = torch.device("cuda:0")
@@ -560,8 +568,88 @@ def mx6_rows(rounds, stream):
         del bufs
     mx.release()
     mx4.release()
+    mx6_tree_rows(rows, stream, take_all)
     mx6.release()
     return rows
+
+
+def mx6_tree_rows(rows, stream, take_all=None):
+    """The tree rows of --mx6, into rows[r], per format: the fold-only op and the one-pass op interleaved within each
+    round, on the fold rows' kind of data."""
+    from chiara_amd import mx6
+
+    dev = torch.device("cuda:0")
+    tile_t = mx6.mx6_type()
+    fptr = lambda L, name: ctypes.cast(getattr(L, name), ctypes.c_void_p).value
+    ab = ctypes.CDLL(os.path.abspath(take_all)) if take_all else None  # a -DCHR_MX6_TREE_TAKE_ALL=1 build (make mx6_tree_ab)
+
+    def operand(fmt, tiles):
+        nvals = tiles * mx6.TILE_VALUES
+        x = torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
+        t = torch.empty(tiles * mx6.TILE_BYTES, dtype=torch.uint8, device=dev)
+        ca.check(mx6.quantize(t, x, nvals, ca.FLOAT32, fmt, stream))
+        return t
+
+    shapes = [(nl, tt, reps) for nl in (2, 4, 8) for tt, reps in ((31775, 240), (127100, 80))]
+    shapes += [(8, 47662, 160), (8, 63550, 120), (8, 95325, 100)]  # --mx4's sizes between the two
+    for fname, fmt in (("e2m3", mx6.E2M3), ("e3m2", mx6.E3M2)):
+        taken = mx6.mx6_sum_tree(fmt)
+        launcher, tree_op = getattr(ab or mx6.mx6_tree_lib(), f"chr_mx6_{fname}_sum_tree_launch"), taken
+        if ab:  # the same kernels, nothing declined for speed
+            tree_op = ca.op_create(fptr(mx6.mx6_lib(), f"chr_mx6_{fname}_sum_fold"), commute=True,
+                                   tree=fptr(ab, f"chr_mx6_{fname}_sum_tree_launch"))
+        launcher.argtypes = [ctypes.POINTER(UserTree), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        launcher.restype = ctypes.c_int
+        for nl, tt, reps in shapes:
+            comb, swaps = TREE_PROGS[nl]
+            tb = tt * mx6.TILE_BYTES
+            sets = max(1, int(2.25 * (1 << 30)) // ((nl + 1) * tb))
+            bufs = [[operand(fmt, tt) for _ in range(nl + 1)] for _ in range(sets)]
+            trees = []
+            for s in bufs:
+                t = UserTree()
+                t.out = s[nl].data_ptr()
+                for j in range(nl):
+                    t.leaves[j] = s[j].data_ptr()
+                    t.comb[j] = comb[j]
+                t.nleaves, t.n = nl, tt
+                trees.append(t)
+            torch.cuda.synchronize()
+            for r in range(len(rows)):
+                for name, op in (("folds", mx6.mx6_sum(fmt)), ("tree", tree_op)):
+                    def go(i, op=op):
+                        s = bufs[i % sets]
+                        ca.check(ca.reduce_tree(s[nl], s[:nl], comb, swaps, tt, tile_t, op, stream))
+                    ms = timed(go, reps)
+                    rows[r][f"{fname}_tree{nl}_{tt}tiles_mx6_{name}_ms"] = round(ms, 4)
+                    rows[r][f"{fname}_tree{nl}_{tt}tiles_mx6_{name}_frac"] = round((nl + 1) * tb / (ms * 1e-3) / HBM_PEAK, 4)
+                # 0: the launcher's own 16 per CU; 12: what the library asks for beside RCCL; 26: all the LDS stack allows
+                for cap in (0, 12, 16, 26) if nl == 8 and tt in (31775, 127100) else ():
+                    def go(i, cap=cap):
+                        return launcher(ctypes.byref(trees[i % sets]), 1, tile_t, cap, stream.cuda_stream, None)
+                    took = go(0) == 0  # a launcher that declines has enqueued nothing: the row is null
+                    rows[r][f"{fname}_tree8_{tt}tiles_mx6_launcher_cap{cap}_ms"] = round(timed(go, reps), 4) if took else None
+            del bufs, trees
+        # the C4-shaped allreduce, 8 virtual ranks, 2 x 127 100 tiles per rank (eight 31 775-tile trees to a call)
+        nr, cnt = 8, 254200
+        g = ca.LocalGroup(nr, 0)
+        sends = [operand(fmt, cnt) for _ in range(nr)]
+        recvs = [torch.empty(cnt * mx6.TILE_BYTES, dtype=torch.uint8, device=dev) for _ in range(nr)]
+        for r in range(len(rows)):
+            for name, op in (("folds", mx6.mx6_sum(fmt)), ("tree", taken)):
+                for _ in range(2):
+                    ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(5):
+                    ca.check(g.all_reduce_radix_batch(sends, recvs, cnt, tile_t, op, 4, 4))
+                torch.cuda.synchronize()
+                rows[r][f"{fname}_localgroup8_k4b4_{cnt}tiles_mx6_{name}_ms"] = round((time.perf_counter() - t0) / 5 * 1e3, 3)
+        g.destroy()
+        del sends, recvs
+        if ab:
+            ca.op_free(tree_op)
+    mx6.tree_release()
 
 
 def mx8_operand(data, tiles, quantize):
@@ -850,6 +938,9 @@ def main():
                     help="with --mx4: a -DCHR_MX4_TREE_TAKE_ALL=1 build of mx4_tree_ops.hip (make mx4_tree_ab); the "
                          "one-pass tree rows run its launcher")
     ap.add_argument("--mx6", action="store_true", help="only the MXFP6 rows of libchiara_mx6.so (see above)")
+    ap.add_argument("--mx6-take-all", metavar="LIB.so",
+                    help="with --mx6: a -DCHR_MX6_TREE_TAKE_ALL=1 build of mx6_tree_ops.hip (make mx6_tree_ab); the "
+                         "one-pass tree rows run its launchers")
     ap.add_argument("--mxint8", action="store_true", help="only the MXINT8 rows of libchiara_mxint8.so (see above)")
     ap.add_argument("--mxint8-f32", metavar="LIB.so",
                     help="with --mxint8: a -DCHR_MXI8_INT=0 build of mxint8_ops.hip (make mxint8_ab); its fold as mxint8_f32")
@@ -902,7 +993,9 @@ def main():
         return
     if a.mx6:
         out = {"tool": "tools/userop_bench.py --mx6", "ops_lib": "libchiara_mx6.so", "mx_lib": "libchiara_mx.so",
-               "mx4_lib": "libchiara_mx4.so", "rounds": mx6_rows(a.rounds, stream)}
+               "mx4_lib": "libchiara_mx4.so", "tree_lib": "libchiara_mx6_tree.so",
+               "take_all_lib": a.mx6_take_all and os.path.basename(a.mx6_take_all),
+               "rounds": mx6_rows(a.rounds, stream, a.mx6_take_all)}
         line = json.dumps(out)
         print(line)
         if a.out:
