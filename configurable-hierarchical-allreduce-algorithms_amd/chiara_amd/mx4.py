@@ -18,7 +18,11 @@ libchiara_mx4.so is an error.
 mx4_sum's op carries the fold launcher alone, so the flat schedules' expression trees run fold by fold.
 mx4_sum_tree() is the same SUM with the tree kernel of libchiara_mx4_tree.so (include/chiara_mx4_tree.h): one HBM
 pass per tree of up to 31 775 tiles (larger ones and single-fold chains stay with the folds, which measured faster
-there), the same bytes; tree_stats() counts its launcher's calls and tree_release() frees its op."""
+there), the same bytes; tree_stats() counts its launcher's calls and tree_release() frees its op.
+
+mx4_sum_sr() and quantize_sr() are the SUM and the quantize with stochastic rounding of libchiara_mx4_sr.so
+(include/chiara_mx4_sr.h) on the same tiles, for gradients: sr_set_seed(step) on every rank before each collective,
+dequantize() as before, sr_stats() and sr_release() like their namesakes."""
 import ctypes
 import os
 
@@ -143,4 +147,67 @@ def tree_stats(reset=False):
     (chr_mx4_tree_stats)."""
     c = (ctypes.c_long * 4)()
     mx4_tree_lib().chr_mx4_tree_stats(c, 1 if reset else 0)
+    return tuple(c)
+
+
+# ---- stochastic rounding: libchiara_mx4_sr.so (include/chiara_mx4_sr.h) ----------------------------------------------
+
+MX4_SR_LIB_PATH = os.path.join(HERE, "libchiara_mx4_sr.so")
+
+_mx4_sr_lib = None
+
+
+def mx4_sr_lib():
+    """libchiara_mx4_sr.so, loaded on first use (libchiara_mx4.so and libchiara.so, its dependencies, are this
+    process's copies)."""
+    global _mx4_sr_lib
+    if _mx4_sr_lib is None:
+        mx4_lib()
+        if not os.path.exists(MX4_SR_LIB_PATH):
+            raise ImportError(f"libchiara_mx4_sr.so not found at {MX4_SR_LIB_PATH}; build it with `make -C {PKG_ROOT}` "
+                              f"(hipcc --offload-arch=gfx950) or __graft_entry__.build()")
+        L = ctypes.CDLL(MX4_SR_LIB_PATH)
+        vp, sz, i, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
+        L.chr_mx4_sr_sum.argtypes = [ctypes.POINTER(ctypes.c_int)]
+        L.chr_mx4_sr_sum.restype = ctypes.c_int
+        L.chr_mx4_sr_set_seed.argtypes = [u32]
+        L.chr_mx4_sr_set_seed.restype = None
+        L.chr_mx4_sr_quantize.argtypes = [vp, vp, sz, i, u32, vp]
+        L.chr_mx4_sr_quantize.restype = ctypes.c_int
+        L.chr_mx4_sr_release.argtypes = []
+        L.chr_mx4_sr_release.restype = ctypes.c_int
+        L.chr_mx4_sr_stats.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.c_int]
+        L.chr_mx4_sr_stats.restype = None
+        _mx4_sr_lib = L
+    return _mx4_sr_lib
+
+
+def mx4_sum_sr():
+    """The op code of the SUM that rounds stochastically (chr_mx4_sr_sum) on mx4_type()'s tiles: the fold launcher
+    alone, so trees run fold by fold.  The random bits are a function of the seed, the place in the tile and the
+    operands' bits: the same bytes on every rank and under every slicing.  The same code until sr_release()."""
+    return _code(mx4_sr_lib().chr_mx4_sr_sum, "chr_mx4_sr_sum")
+
+
+def sr_set_seed(seed):
+    """The seed of every later SR SUM of this process (chr_mx4_sr_set_seed; default 0), read at enqueue time.  Every
+    rank sets the same value before the same collective, and a new one every step: unbiasedness is over seeds."""
+    mx4_sr_lib().chr_mx4_sr_set_seed(int(seed) & 0xFFFFFFFF)
+
+
+def quantize_sr(tiles, src, n, src_type, seed, stream=None):
+    """tiles = Q_sr(src) (chr_mx4_sr_quantize): quantize() with stochastic rounding under `seed`, keyed on the tile's
+    index as well.  Enqueued on `stream`; returns the status code.  dequantize() reads the result."""
+    return mx4_sr_lib().chr_mx4_sr_quantize(_addr(tiles), _addr(src), n, int(src_type), int(seed) & 0xFFFFFFFF, _stream(stream))
+
+
+def sr_release():
+    """Free the op libchiara_mx4_sr.so registered (chr_mx4_sr_release); returns the status code."""
+    return mx4_sr_lib().chr_mx4_sr_release()
+
+
+def sr_stats(reset=False):
+    """(fold-launcher calls, calls it declined, kernels it enqueued) since the last reset (chr_mx4_sr_stats)."""
+    c = (ctypes.c_long * 3)()
+    mx4_sr_lib().chr_mx4_sr_stats(c, 1 if reset else 0)
     return tuple(c)

@@ -61,7 +61,10 @@
    the one-pass tree rows and the direct launcher rows need --mx4-take-all LIB.so, a build that takes every tree (make
    mx4_tree_ab), registered here with libchiara_mx4.so's fold launcher; without it the tree rows run the shipped op,
    whose declined trees take the folds, and a direct launcher row whose tree the shipped launcher declines is
-   recorded as null.  The allreduce rows always run the shipped op.  Only these rows run.
+   recorded as null.  The allreduce rows always run the shipped op.  Between the fold rows and the tree rows come the
+   sr_ rows (mx4_sr_rows): libchiara_mx4_sr.so's stochastic-rounding fold (mx4.mx4_sum_sr) beside the RNE MX4 fold, m = 1
+   and 3 in place on one HBM-cold rotation, and mx4.quantize_sr beside mx4.quantize from f32, each as GB/s and as the
+   SR / RNE ratio.  Only these rows run.
 
  * --mx6: the MXFP6 block-scaled SUMs of libchiara_mx6.so (chiara_amd/mx6.py, include/chiara_mx6.h), E2M3 and E3M2,
    beside the MX E4M3 SUM of libchiara_mx.so and the MX4 SUM of libchiara_mx4.so on the same kind of values: folds
@@ -519,9 +522,57 @@ def mx4_rows(rounds, stream, take_all=None):
                     rows[r][f"fold_m{m}_mx4_sum_{unit}"] / rows[r][f"fold_m{m}_mx_e4m3_sum_{unit}"], 3)
         del bufs
     mx.release()
+    mx4_sr_rows(rows, stream)
     mx4_tree_rows(rows, stream, take_all)
     mx4.release()
     return rows
+
+
+def mx4_sr_rows(rows, stream):
+    """The SR rows of --mx4, into rows[r]: libchiara_mx4_sr.so's fold beside the RNE MX4 fold, m = 1 and 3 in place on
+    one HBM-cold rotation, alternating within each round; then quantize_sr beside quantize from f32 (read 4 bytes and
+    write 17 / 32 of a byte per value)."""
+    from chiara_amd import mx4
+
+    dev = torch.device("cuda:0")
+    tiles = rows[0]["tiles"]
+    nvals, nbytes = tiles * mx4.TILE_VALUES, tiles * mx4.TILE_BYTES
+    tile_t = mx4.mx4_type()
+    ops = (("mx4_sum", mx4.mx4_sum()), ("mx4_sum_sr", mx4.mx4_sum_sr()))
+
+    def source():
+        return torch.randn(nvals // 32, 32, device=dev) * torch.exp2(torch.randint(-20, 21, (nvals // 32, 1), device=dev))
+
+    def operand():
+        t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ca.check(mx4.quantize(t, source(), nvals, ca.FLOAT32, stream))
+        return t
+
+    for m in (1, 3):
+        sets = [[operand() for _ in range(m + 1)] for _ in range(max(1, int(2.25 * (1 << 30)) // ((m + 1) * nbytes)))]
+        torch.cuda.synchronize()
+        for r, row in enumerate(rows):
+            mx4.sr_set_seed(r + 1)
+            for name, op in ops:
+                def go(i, op=op):  # acc in place, m inputs: m + 2 units of traffic
+                    s = sets[i % len(sets)]
+                    ca.check(ca.reduce_multi(s[0], s[0], s[1:], tiles, tile_t, op, stream))
+                row[f"sr_fold_m{m}_{name}_GBps"] = round((m + 2) * nbytes / timed(go, 60) / 1e6, 1)
+            row[f"sr_fold_m{m}_sr_over_rne"] = round(row[f"sr_fold_m{m}_mx4_sum_sr_GBps"] / row[f"sr_fold_m{m}_mx4_sum_GBps"], 3)
+        del sets
+    pairs = [(source(), torch.empty(nbytes, dtype=torch.uint8, device=dev)) for _ in range(max(1, int(2.25 * (1 << 30)) // (4 * nvals + nbytes)))]
+    torch.cuda.synchronize()
+    for r, row in enumerate(rows):
+        for name, q in (("quantize", lambda t, x: mx4.quantize(t, x, nvals, ca.FLOAT32, stream)),
+                        ("quantize_sr", lambda t, x: mx4.quantize_sr(t, x, nvals, ca.FLOAT32, r + 1, stream))):
+            def go(i, q=q):
+                x, t = pairs[i % len(pairs)]
+                ca.check(q(t, x))
+            row[f"sr_{name}_f32_GBps"] = round((4 * nvals + nbytes) / timed(go, 60) / 1e6, 1)
+        row["sr_quantize_f32_sr_over_rne"] = round(row["sr_quantize_sr_f32_GBps"] / row["sr_quantize_f32_GBps"], 3)
+    del pairs
+    mx4.sr_set_seed(0)
+    mx4.sr_release()
 
 
 def mx6_rows(rounds, stream, take_all=None):
